@@ -8,12 +8,15 @@ One "step" = one RK4 step of every density matrix in the per-GPU batch
 matrix steps/s over all ranks (weak scaling: each rank owns its own batch;
 no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  The CPU baseline (rank 0, N=1 only) is the
-oracle's reference-faithful scipy.sparse csr restatement of oqs._lindblad,
-timed on a bounded sample on this host.
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs and no more: it sets up, warms up, times ONE
+region of exactly --steps steps, writes the propagated density matrices if --dump-outputs is given, and prints
+the line.  --full adds everything else: the headline as the median of HEADLINE_REPS such regions, the batch sweep,
+the secondary legs (2DES, Redfield, dense superoperator, SPO2 / SPO3, DEOM), the CPU baselines and the detail side
+file.  The CPU baseline (rank 0, N=1 only) is the oracle's reference-faithful scipy.sparse csr restatement of
+oqs._lindblad, timed on a bounded sample on this host.
 """
 from __future__ import annotations
 
@@ -1233,6 +1236,25 @@ def write_detail(out, path):
         return f"not written ({e})"
 
 
+DUMP_MAX_BYTES = 32 * 2 ** 20   # per dump, well under the 64 MB a comparison of two builds may hold
+
+
+def dump_outputs(rho, path):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, the propagated density matrices
+    (lindblad_rk4 updates rho [B, N, N] in place), as path/rho.npy, float64 [b, N, N, 2] (re, im).  A batch over
+    DUMP_MAX_BYTES is cut to a fixed seeded sample of its matrices, whose batch indices go to path/rho_index.npy."""
+    B, N = rho.shape[0], rho.shape[-1]
+    idx = np.arange(B)
+    keep = max(1, DUMP_MAX_BYTES // (N * N * 16))
+    if B > keep:
+        idx = np.sort(np.random.default_rng(11).choice(B, size=keep, replace=False))
+    import torch
+    sel = rho[torch.from_numpy(idx).to(rho.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rho.npy"), np.ascontiguousarray(sel).view(np.float64).reshape(len(idx), N, N, 2))
+    np.save(os.path.join(path, "rho_index.npy"), idx.astype(np.float64))
+
+
 def _pick(d, *keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d}
 
@@ -1321,6 +1343,12 @@ def main():
     ap.add_argument("--N", type=int, default=128)
     ap.add_argument("--nc", type=int, default=1)
     ap.add_argument("--dt", type=float, default=1e-3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the median over HEADLINE_REPS timed regions, the "
+                         "batch sweep, the secondary legs, the CPU baselines and the detail side file (the --no-* "
+                         "options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the propagated density matrices to DIR/rho.npy (dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--general", action="store_true",
                     help="force the general (non-Hermitian) GLF kernel instead of the Hermitian one")
@@ -1349,6 +1377,9 @@ def main():
     ap.add_argument("--detail", default=None,
                     help="side file for every leg's full record (default gpurun_out/bench_detail.json)")
     args = ap.parse_args()
+    if not args.full:   # a plain run is the headline alone: every other leg and baseline is off
+        args.no_cpu = args.no_2des = args.no_redfield = args.no_superop = True
+        args.no_spo = args.no_spo3 = args.no_deom = True
 
     import torch
     import torch.distributed as dist
@@ -1387,9 +1418,15 @@ def main():
     batch_sweep = {}
     # untimed: ~30 ms of B = 64 work first, so that neither timed leg runs through the idle-clock ramp (the B = 1 leg
     # measured 47.x k steps/s as the first work of the process against 49.7k behind other work)
-    lindblad_rk4(Ht, Ct, rho[:64].clone(), args.dt, 100, hermitian=False if args.general else None)
+    ramp = rho[:64].clone()
+    lindblad_rk4(Ht, Ct, ramp, args.dt, 100, hermitian=False if args.general else None)
+    if not args.full:
+        # a plain run skips the sweep: the B = 64 leg's 300 steps run here untimed, so that the headline still starts
+        # at the clocks a running job has
+        lindblad_rk4(Ht, Ct, ramp, args.dt, 300, hermitian=False if args.general else None)
+    del ramp
     torch.cuda.synchronize(dev)
-    for Bs in (1, 64):
+    for Bs in ((1, 64) if args.full else ()):
         rs = rho[:Bs].clone()
         _lib.take_path()
         lindblad_rk4(Ht, Ct, rs, args.dt, 2, hermitian=False if args.general else None)
@@ -1420,19 +1457,22 @@ def main():
                          "traffic": (measured_traffic("glf_single_herm_kernel<1,true>_b1" if hsingle else
                                                       "glf_single_kernel<4,1,true,true>_b1", ss)
                                      if (Bs, N, nc) == (1, 128, 1) else None)}}
-    single_rate = batch_sweep["1"]["dm_steps_per_s"]
+    single_rate = batch_sweep["1"]["dm_steps_per_s"] if args.full else None
 
-    progress("lindblad batch sweep done")
+    progress("lindblad batch sweep done" if args.full else "lindblad ramp done")
 
     # warm-up
-    lindblad_rk4(Ht, Ct, rho, args.dt, args.warmup, hermitian=herm)
+    if args.warmup > 0:
+        lindblad_rk4(Ht, Ct, rho, args.dt, args.warmup, hermitian=herm)
     torch.cuda.synchronize(dev)
 
-    # the headline is the MEDIAN of HEADLINE_REPS timed regions, each EXACTLY args.steps steps of the
-    # whole batch bracketed by a barrier + torch.cuda.synchronize() on both sides, each rep's time the max over ranks
-    # (the reps continue the same trajectories: every rep is the same work, steps args.steps * k .. * (k + 1))
+    # a timed region is EXACTLY args.steps steps of the whole batch bracketed by a barrier +
+    # torch.cuda.synchronize() on both sides, its time the max over ranks.  A plain run times one region, so --steps is
+    # the number of timed steps; --full reports the MEDIAN of HEADLINE_REPS regions (the reps continue the same
+    # trajectories: every rep is the same work, steps args.steps * k .. * (k + 1))
+    reps = HEADLINE_REPS if args.full else 1
     samples, kern_samples = [], []
-    for _ in range(HEADLINE_REPS):
+    for _ in range(reps):
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         if world > 1:
             dist.barrier()
@@ -1456,8 +1496,11 @@ def main():
     # sanity: trace preserved (cheap, outside the timed region)
     tr = torch.diagonal(rho, dim1=1, dim2=2).sum(-1)
     tr_err = float((tr - 1).abs().max().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(rho, args.dump_outputs)
 
     progress("lindblad headline leg done")
+    leg_done = progress if args.full else (lambda msg: None)   # a plain run has no further legs to report
     twodes = None
     if not args.no_2des:
         twodes, sig, ens_in = bench_2des(dev, world, rank, args.ens, args.ens_reps)
@@ -1504,27 +1547,27 @@ def main():
     def pair(r):
         return r if isinstance(r, tuple) else (r, None)
 
-    progress("2des legs done")
+    leg_done("2des legs done")
     redfield = None
     if not args.no_redfield:
         redfield, rf_sol = pair(guarded(bench_redfield, dev, args.steps, B))
 
-    progress("redfield leg done")
+    leg_done("redfield leg done")
     superop = None
     if not args.no_superop:
         superop, so_in = pair(guarded(bench_superop, dev))
 
-    progress("superop leg done")
+    leg_done("superop leg done")
     spo = None
     if not args.no_spo:
         spo = guarded(bench_spo2, dev, args.spo_steps)
 
-    progress("spo2 leg done")
+    leg_done("spo2 leg done")
     spo3 = None
     if not args.no_spo3:
         spo3 = guarded(bench_spo3, dev)
 
-    progress("spo3 leg done")
+    leg_done("spo3 leg done")
     deom = None
     if not args.no_deom:
         deom = guarded(bench_deom, dev, args.deom_steps, args.deom_batch)
@@ -1533,7 +1576,7 @@ def main():
     # At world > 1 it is opt-in (--deom-banded-ranks): a collective leg cannot be guarded per rank (one rank's
     # exception would leave the others waiting in the all-gather), and the halo is 2.5x the owned rows at 8 bands, so
     # it is a capacity tool, not a speed-up, for the bench hierarchy.  World 1 runs the 8-band loopback.
-    progress("deom leg done")
+    leg_done("deom leg done")
     deom_corr4 = None
     if world == 1 and not args.no_deom and not args.no_deom_corr4:
         deom_corr4 = guarded(bench_deom_corr4, dev)
@@ -1563,7 +1606,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(wall_max / args.steps * 1e3, 4),
-            "timing": {"reps": HEADLINE_REPS, "statistic": "median over reps of (max over ranks of the wall time of "
+            "timing": {"reps": reps, "statistic": "median over reps of (max over ranks of the wall time of "
                                                            "one timed region of exactly `steps` steps)",
                        "ms_per_step_samples": [round(x / args.steps * 1e3, 4) for x in samples]},
             "higher_is_better": True,
@@ -1600,7 +1643,7 @@ def main():
                 "launch_ms": round(kern_s * 1e3, 3),
                 "launch_ms_samples": [round(x * 1e3, 3) for x in kern_samples],
             },
-            "single_trajectory_steps_per_s": round(single_rate, 2),
+            "single_trajectory_steps_per_s": round(single_rate, 2) if args.full else None,
             "batch_sweep": batch_sweep,
             "trace_err": tr_err,
         }
@@ -1634,7 +1677,8 @@ def main():
             out.setdefault("secondary", {})["deom_corr4"] = deom_corr4
         if deom_banded is not None:
             out.setdefault("secondary", {})["deom_banded"] = deom_banded
-        detail = write_detail(out, args.detail)
+        # the side file belongs to --full; a plain run writes it only where --detail names one
+        detail = write_detail(out, args.detail) if args.full or args.detail else None
         print(json.dumps(compact_line(out, detail)), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -11,6 +11,28 @@ from conftest import ROOT
 sys.path.insert(0, ROOT)
 
 
+def test_dump_outputs_full_batch_and_seeded_sample(tmp_path):
+    """bench.dump_outputs: float64 (re, im) of the states; a batch over DUMP_MAX_BYTES is cut to the same seeded
+    sample of its matrices on every call, whose indices are written beside it."""
+    import numpy as np
+    import torch
+    import bench
+    N = 32
+    keep = bench.DUMP_MAX_BYTES // (N * N * 16)
+    rng = np.random.default_rng(0)
+    for B in (3, keep + 5):
+        rho = rng.standard_normal((B, N, N)) + 1j * rng.standard_normal((B, N, N))
+        for d in ("a", "b"):
+            bench.dump_outputs(torch.from_numpy(rho), str(tmp_path / f"{B}{d}"))
+        x, idx = np.load(tmp_path / f"{B}a" / "rho.npy"), np.load(tmp_path / f"{B}a" / "rho_index.npy")
+        assert x.dtype == np.float64 and idx.dtype == np.float64
+        assert x.shape == (min(B, keep), N, N, 2) and x.nbytes <= bench.DUMP_MAX_BYTES <= 64e6
+        assert np.array_equal(idx, np.arange(B)) if B <= keep else len(np.unique(idx)) == keep
+        assert np.array_equal(x[..., 0] + 1j * x[..., 1], rho[idx.astype(int)])
+        assert np.array_equal(idx, np.load(tmp_path / f"{B}b" / "rho_index.npy"))
+        assert np.array_equal(x, np.load(tmp_path / f"{B}b" / "rho.npy"))
+
+
 def test_compact_line_keys_and_length():
     import bench
     out = json.load(open(os.path.join(ROOT, "profiles", "r04", "bench_r04f_detail.json")))

@@ -228,8 +228,24 @@ def test_deom_corr4_oracle_matches_reference():
     for lcr in ["llll", "lrlr", "lccc"]:
         cw = od.correlation_4op_3t(P, *args, [sx] * 4, g["rho0"], float(g["T"]), g["wx"], g["wy"], lcr=lcr)
         assert relerr(cw, g["cw_" + lcr]) < 1e-12, lcr
-    cw = od.correlation_4op_3t(P, *args, [sz, sx, sx, sz], g["rho0"], float(g["T"]), g["wx"], g["wy"], if_full=False)
-    assert relerr(cw, g["cw_cut_llll"]) < 1e-12
+    # The reference's default cuts (min(Re) * 0.5 < Re < max(Re) * 1.1) sit on two eigenvalues of this hierarchy to the
+    # last bits, so the rounding of the eigensolver, which changes with the BLAS thread count and the CPU, decides what
+    # is kept.  The fixture's run kept 100 of the 140: it dropped the eigenvalue at Re = min(Re) / 2 (its term is 7e-9
+    # of the signal) and kept the steady state (Re = 0 up to rounding, 96 % of the signal), which `Re < 1.1 max(Re)`
+    # keeps only when that rounding came out positive.  The cuts below select the fixture's set on every host: the
+    # lower one 1e-6 higher, the upper one on the steady state's far side whatever its sign; the next eigenvalues are
+    # 0.42 away from either cut.  With the set fixed, this run and the fixture's differ by the rounding of two eigen
+    # decompositions: the signal chains two similarity transforms V^-1 A V, each good to eps cond(V), so the bound is
+    # eps cond(V)^2 with a factor 10 for the sums over the 140 modes (cond(V) = 58: 7.5e-12).  The old 1e-12 held only
+    # where the eigensolver's rounding repeated the fixture's bit for bit.
+    import scipy.linalg as la
+    lam, V = la.eig(P)                                   # the oracle's own eigensolver call
+    top = np.real(lam).max()
+    assert abs(top) < 1e-12
+    bound = 10 * np.finfo(float).eps * np.linalg.cond(V) ** 2
+    cw = od.correlation_4op_3t(P, *args, [sz, sx, sx, sz], g["rho0"], float(g["T"]), g["wx"], g["wy"], if_full=False,
+                               cut_off_min=0.5 - 1e-6, cut_off_max=1.1 if top > 0 else 0.9)
+    assert relerr(cw, g["cw_cut_llll"]) < bound < 1e-11
 
 
 @pytest.mark.parametrize("name", ["spo2_20x20", "spo2_96x80", "spo2_67x45_ns3", "spo2_12x10_ns9"])

@@ -10,7 +10,7 @@ BENCH_MAPS=$O/maps_torch.txt timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --outp
 rc=$?
 echo "torch control rc=$rc"; tail -2 $O/torch.log
 if [ $rc -ne 0 ]; then python3 $R/tools/resolve_frames.py $O/torch.log $O/maps_torch.txt > $O/frames_torch.txt 2>&1; head -40 $O/frames_torch.txt; exit 0; fi
-BENCH_MAPS=$O/maps.txt timeout -k 10 250 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- python3 $R/bench.py --steps 20 --warmup 2 --no-cpu --no-2des --no-spo --no-redfield --no-superop > $O/fetch.log 2>&1
+BENCH_MAPS=$O/maps.txt timeout -k 10 250 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- python3 $R/bench.py --steps 20 --warmup 2 --full --no-cpu --no-2des --no-spo --no-redfield --no-superop > $O/fetch.log 2>&1
 rc=$?
 echo "bench deom legs rc=$rc"; grep -v '^\s*@' $O/fetch.log | tail -3
 if [ $rc -ne 0 ]; then python3 $R/tools/resolve_frames.py $O/fetch.log $O/maps.txt > $O/frames.txt 2>&1; head -40 $O/frames.txt; fi
