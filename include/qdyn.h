@@ -476,6 +476,23 @@ int qd_tdse_rk4(const qd_c128* H, qd_c128* psi, int B, int N, double dt,
                 int ne, qd_c128* obs, void* stream);
 
 /*
+ * Closed-system multi-time correlation functions (pyqed/mol.py:1475-1536
+ * SESolver.correlation_3op_1t / correlation_3op_2t): for every psi_b
+ *   ket_b(0) = C psi_b,  bra_b(0) = A^dagger psi_b,
+ * both advanced by the RK4 of qd_tdse_rk4 (H need not be Hermitian: nothing is
+ * derived by conjugation), and
+ *   corr[b][j] = sum_r conj(bra_b(j)[r]) (Bop ket_b(j))[r],  j = 0 .. ntau-1
+ * (j = 0 before any step, ntau - 1 steps in all).
+ *   H, A, Bop, C [N][N]; psi [B][N] read only; corr [B][ntau].
+ * The 2B states run as one batch; no state is saved (scratch independent of
+ * ntau).  All sums in fixed order: repeated calls agree bit for bit.
+ * Any N >= 1, B >= 1, ntau >= 1.
+ */
+int qd_tdse_pair_corr(const qd_c128* H, const qd_c128* A, const qd_c128* Bop,
+                      const qd_c128* C, const qd_c128* psi, int B, int N,
+                      double dt, int ntau, qd_c128* corr, void* stream);
+
+/*
  * Laser-driven TDSE (pyqed/mol.py:1862-1958 driven_dynamics, reached from
  * Mol.run / SESolver.run with a pulse, mol.py:660-675 / 1430-1456):
  *   H_k = H0 - sum_d f_d(t_k) Hd_d,  t_k = t0 + k nout dt,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "qd_resolvent_sum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "qd_tdse_rk4": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p, c_int,
                             c_void_p, c_void_p]),
+    "qd_tdse_pair_corr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
+                                  c_void_p, c_void_p]),
     "qd_tdse_driven_rk4": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "qd_photon_echo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,

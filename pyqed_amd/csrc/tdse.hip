@@ -279,6 +279,207 @@ int tdse_gemm_steps(const c128* H, c128* psi, int B, int N, double dt, int nstep
   return QD_OK;
 }
 
+// ---- pair correlations (qd_tdse_pair_corr; SESolver.correlation_3op_1t / _2t, mol.py:1475-1536): for every psi_b
+// the ket C psi_b and the bra A^dagger psi_b are propagated side by side as one batch X = [kets; bras] of 2B states
+// through the stages above, and after every step corr[b][j] = sum_r conj(bra_b[r]) (Bop ket_b)[r].  No state is
+// saved: scratch does not depend on ntau.  Every sum runs in a fixed order (no atomics), so corr is reproducible
+// bit for bit.
+
+// row path start: ket_b[r] = sum_j C[r][j] psi_b[j], a wave per row; grid (ceil(N / 4), B)
+__global__ __launch_bounds__(256) void tdse_pair_ket_rows_kernel(const c128* C, const c128* psi_g, int N, c128* ket) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= N) return;
+  const size_t b = blockIdx.y;
+  const c128 y = wave_row_dot(C + (size_t)r * N, psi_g + b * N, N);
+  if ((threadIdx.x & 63) == 0) ket[b * N + r] = y;
+}
+
+// row path start: bra_b[r] = sum_j conj(A[j][r]) psi_b[j].  The sum runs down a column of A, so the lanes of a wave
+// take 64 neighbouring columns r (1 KB pieces of the rows of A) and the four waves the rows j = w, w + 4, ...; their
+// partial sums are added in wave order.  grid (ceil(N / 64), B)
+__global__ __launch_bounds__(256) void tdse_pair_bra_cols_kernel(const c128* A, const c128* psi_g, int N, c128* bra) {
+  __shared__ c128 red[4][64];
+  const int c = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = blockIdx.x * 64 + c;
+  const c128* psi = psi_g + (size_t)blockIdx.y * N;
+  double sr = 0.0, si = 0.0;
+  if (r < N) {
+    for (int j = w; j < N; j += 4) {
+      const c128 a = A[(size_t)j * N + r], v = psi[j];
+      sr += a.re * v.re + a.im * v.im;
+      si += a.re * v.im - a.im * v.re;
+    }
+  }
+  red[w][c] = cmk(sr, si);
+  __syncthreads();
+  if (w == 0 && r < N)
+    bra[(size_t)blockIdx.y * N + r] = cadd(cadd(red[0][c], red[1][c]), cadd(red[2][c], red[3][c]));
+}
+
+// row path: part[b][r] = conj(bra_b[r]) (Bop ket_b)_r with X = [kets; bras] [2B][N]; grid (ceil(N / 4), B).  The rows
+// are summed by tdse_obs_sum_kernel (ne = 1).
+__global__ __launch_bounds__(256) void tdse_pair_obs_rows_kernel(const c128* Bop, const c128* X, int B, int N,
+                                                                 c128* part) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= N) return;
+  const size_t b = blockIdx.y;
+  const c128 y = wave_row_dot(Bop + (size_t)r * N, X + b * N, N);
+  if ((threadIdx.x & 63) == 0) part[b * N + r] = cmul(cconj(X[(B + b) * N + r]), y);
+}
+
+// GEMM path: the padded right operand [Np][Np] that applies an operator M [N][N] to every row of X in X * out:
+// mode 0: out[j][r] = M[r][j] (rows of X M^T are M x), mode 1: out[j][r] = conj(M[j][r]) (rows are M^dagger x).
+__global__ void tdse_pack_op_kernel(const c128* M, int N, int Np, int mode, c128* out) {
+  const size_t tot = (size_t)Np * Np;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(e / Np), r = (int)(e % Np);
+    c128 v = cmk(0, 0);
+    if (j < N && r < N) v = mode == 0 ? M[(size_t)r * N + j] : cconj(M[(size_t)j * N + r]);
+    out[e] = v;
+  }
+}
+
+// GEMM path start: rows row0 .. row0 + B - 1 of P [Bp][Np] = sum_s slabs[s] (fixed order) of a [Bk][Np] product;
+// zero_rest != 0 also clears every other row of P.
+__global__ void tdse_pair_start_gemm_kernel(const c128* slabs, int S, size_t tot, int B, int Bp, int Np, int row0,
+                                            int zero_rest, c128* P) {
+  const size_t n = (size_t)Bp * Np;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const int row = (int)(e / Np);
+    if (row >= row0 && row < row0 + B) {
+      const size_t src = e - (size_t)row0 * Np;
+      c128 k = slabs[src];
+      k = slab_sum(k, 1, S, [&](int q) { return slabs[(size_t)q * tot + src]; });
+      P[e] = k;
+    } else if (zero_rest) {
+      P[e] = cmk(0, 0);
+    }
+  }
+}
+
+// GEMM path: corr[b][idx] = sum_r conj(bra_b[r]) y_b[r], y = sum_s slabs[s] (fixed order) the rows of Kets * Bop^T
+// ([Bk][Np] slabs), bra_b row B + b of P; one block per b, per-thread strided partials, wave butterfly, 4-wave sum.
+__global__ __launch_bounds__(256) void tdse_pair_obs_gemm_kernel(const c128* slabs, int S, size_t tot, const c128* P,
+                                                                 int B, int Np, int ntau, int idx, c128* corr) {
+  __shared__ c128 red[4];
+  const size_t b = blockIdx.x;
+  const c128* bra = P + (B + b) * Np;
+  double sr = 0.0, si = 0.0;
+  for (int r = threadIdx.x; r < Np; r += 256) {
+    const size_t e = b * Np + r;
+    c128 y = slabs[e];
+    y = slab_sum(y, 1, S, [&](int q) { return slabs[(size_t)q * tot + e]; });
+    const c128 u = bra[r];
+    sr += u.re * y.re + u.im * y.im;
+    si += u.re * y.im - u.im * y.re;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sr += __shfl_xor(sr, off, 64);
+    si += __shfl_xor(si, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cmk(sr, si);
+  __syncthreads();
+  if (threadIdx.x == 0) corr[b * ntau + idx] = cadd(cadd(red[0], red[1]), cadd(red[2], red[3]));
+}
+
+// Rows or GEMM stages for the 2B states, by shape alone.  A GEMM step costs the same for every 2B up to the next
+// multiple of 128 rows while a row step grows with 2B, so the crossover is where the row step reaches the GEMM
+// step (tools/tdse_corr_bench.py, us per step of qd_tdse_pair_corr at 2B states, rows -> GEMM: N = 256: 174 states
+// 81.8 -> 176 states 80.2 (128 states: 64.5 on rows, 75.5 on the GEMMs); N = 512: 62 states 92.9 -> 64 states 95.3,
+// 128 states 96.4; N = 1024: 30 states 156.9 -> 32 states 159.7, 64 states 160.2 (62 states on rows: 294.9);
+// N = 2048: 16 states 346.6 -> 18 states 382.0, the same as 32 states on the GEMMs; 30 states on rows: 737.1).
+// The plain run's thresholds (tdse_rows_run) sit higher at N >= 1024 and lower at N = 256.
+bool tdse_pair_use_gemm(int B, int N) {
+  const long S = 2L * B;
+  return (N >= 2048 && S >= 18) || (N >= 1024 && S >= 32) || (N >= 512 && S >= 64) || (N >= 256 && S >= 176);
+}
+
+int tdse_pair_rows(const c128* H, const c128* A, const c128* Bop, const c128* C, const c128* psi, int B, int N,
+                   double dt, int ntau, c128* corr, hipStream_t st) {
+  const int B2 = 2 * B;
+  const size_t BN = (size_t)B * N;
+  void* w = nullptr;
+  int rc = workspace(WS_MISC, (2 * BN + 6 * BN + BN) * sizeof(c128), &w, st);   // X, stage buffers, part
+  if (rc) return rc;
+  c128* X = (c128*)w;
+  c128* ws = X + 2 * BN;
+  c128* part = ws + 6 * BN;
+  hipLaunchKernelGGL(tdse_pair_ket_rows_kernel, dim3((N + 3) / 4, B), dim3(256), 0, st, C, psi, N, X);
+  QD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(tdse_pair_bra_cols_kernel, dim3((N + 63) / 64, B), dim3(256), 0, st, A, psi, N, X + BN);
+  QD_HIP(hipGetLastError());
+  for (int j = 0; j < ntau; ++j) {
+    if (j) {
+      for (int stage = 0; stage < 4; ++stage) {
+        hipLaunchKernelGGL(tdse_row_stage_kernel<1>, dim3((N + 3) / 4, B2), dim3(256), 0, st, H, X, ws, N, B2, dt,
+                           stage);
+        QD_HIP(hipGetLastError());
+      }
+    }
+    hipLaunchKernelGGL(tdse_pair_obs_rows_kernel, dim3((N + 3) / 4, B), dim3(256), 0, st, Bop, (const c128*)X, B, N,
+                       part);
+    QD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(tdse_obs_sum_kernel, dim3(B), dim3(256), 0, st, (const c128*)part, 1, N, ntau - 1, j, corr);
+    QD_HIP(hipGetLastError());
+  }
+  return QD_OK;
+}
+
+// Rows 0 .. B - 1 of the padded state P [Bp][Np] are the kets and rows B .. 2B - 1 the bras, so the first
+// Bk = 128 ceil(B / 128) <= Bp rows hold every ket and Y = P[0 .. Bk) * Bop^T is one B-row GEMM per step beside the
+// four 2B-row stage GEMMs (rows of Y past B are not read).
+int tdse_pair_gemm(const c128* H, const c128* A, const c128* Bop, const c128* C, const c128* psi, int B, int N,
+                   double dt, int ntau, c128* corr, hipStream_t st) {
+  const int Bk = ceil_div(B, 128) * 128, Bp = ceil_div(2L * B, 128) * 128, Np = ceil_div(N, 128) * 128;
+  const size_t NN = (size_t)Np * Np, BN = (size_t)Bp * Np, KN = (size_t)Bk * Np;
+  constexpr int MAXS = 16;
+  void* w = nullptr;
+  int rc = workspace(WS_TDSE_GEMM, (3 * NN + 3 * BN + (size_t)MAXS * BN) * sizeof(c128), &w, st);
+  if (rc) return rc;
+  c128* mHTp = (c128*)w;
+  c128* BopT = mHTp + NN;
+  c128* opS = BopT + NN;   // C^T, then conj(A): the operands of the two start-up products
+  c128* P = opS + NN;
+  c128* x0 = P + BN;
+  c128* x1 = x0 + BN;
+  c128* slabs = x1 + BN;
+  const int g1 = (int)std::min<size_t>((NN + 255) / 256, 8192), g2 = (int)std::min<size_t>((BN + 255) / 256, 8192);
+  const int gk = (int)std::min<size_t>((KN + 255) / 256, 8192);
+  hipLaunchKernelGGL(tdse_pad_h_kernel, dim3(g1), dim3(256), 0, st, H, N, Np, mHTp);
+  hipLaunchKernelGGL(tdse_pack_op_kernel, dim3(g1), dim3(256), 0, st, Bop, N, Np, 0, BopT);
+  // psi padded to [Bk][Np] in x0 (free until the first stage); dir 0 only reads psi
+  hipLaunchKernelGGL(tdse_pad_psi_kernel, dim3(gk), dim3(256), 0, st, const_cast<c128*>(psi), B, N, Bk, Np, x0, 0);
+  QD_HIP(hipGetLastError());
+  for (int half = 0; half < 2; ++half) {   // kets = Psi C^T into rows [0, B), bras = Psi conj(A) into rows [B, 2B)
+    hipLaunchKernelGGL(tdse_pack_op_kernel, dim3(g1), dim3(256), 0, st, half ? A : C, N, Np, half, opS);
+    QD_HIP(hipGetLastError());
+    int S = 1;
+    if ((rc = cgemm_splitk_slabs(x0, opS, Bk, Np, Np, slabs, MAXS, &S, st))) return rc;
+    hipLaunchKernelGGL(tdse_pair_start_gemm_kernel, dim3(g2), dim3(256), 0, st, (const c128*)slabs, S, KN, B, Bp, Np,
+                       half ? B : 0, half ? 0 : 1, P);
+    QD_HIP(hipGetLastError());
+  }
+  for (int j = 0; j < ntau; ++j) {
+    if (j) {
+      for (int stage = 0; stage < 4; ++stage) {
+        const c128* xin = stage == 0 ? P : ((stage & 1) ? x0 : x1);   // stage 1: x0, 2: x1, 3: x0
+        int S = 1;
+        if ((rc = cgemm_splitk_slabs(xin, mHTp, Bp, Np, Np, slabs, MAXS, &S, st))) return rc;
+        hipLaunchKernelGGL(tdse_gemm_rk4_kernel, dim3(g2), dim3(256), 0, st, (const c128*)slabs, S, BN, P, x0, x1,
+                           (c128*)nullptr, dt, stage);
+        QD_HIP(hipGetLastError());
+      }
+    }
+    int S = 1;
+    if ((rc = cgemm_splitk_slabs(P, BopT, Bk, Np, Np, slabs, MAXS, &S, st))) return rc;
+    hipLaunchKernelGGL(tdse_pair_obs_gemm_kernel, dim3(B), dim3(256), 0, st, (const c128*)slabs, S, KN, (const c128*)P,
+                       B, Np, ntau, j, corr);
+    QD_HIP(hipGetLastError());
+  }
+  return QD_OK;
+}
+
 }  // namespace
 }  // namespace qd
 
@@ -294,6 +495,28 @@ extern "C" int qd_tdse_rk4(const qd_c128* H, qd_c128* psi, int B, int N, double 
   hipStream_t st = (hipStream_t)stream;
   return tdse_rows_run((const c128*)H, (c128*)psi, B, N, dt, nsteps, save_every, (c128*)snap, (const c128*)E, ne,
                        ne ? (c128*)obs : nullptr, st);
+}
+
+extern "C" int qd_tdse_pair_corr(const qd_c128* H, const qd_c128* A, const qd_c128* Bop, const qd_c128* C,
+                                 const qd_c128* psi, int B, int N, double dt, int ntau, qd_c128* corr, void* stream) {
+  WsScope wss_((hipStream_t)stream);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(H && A && Bop && C && psi && corr, "qd_tdse_pair_corr: null pointer");
+  QD_CHECK_ARG(N >= 1 && B >= 1 && ntau >= 1, "qd_tdse_pair_corr: bad sizes N=%d B=%d ntau=%d", N, B, ntau);
+  QD_CHECK_ARG(B <= (1 << 29), "qd_tdse_pair_corr: B=%d too large", B);
+  hipStream_t st = (hipStream_t)stream;
+  if (tdse_pair_use_gemm(B, N)) {
+    note_path("tdse_pair_gemm");
+    return tdse_pair_gemm((const c128*)H, (const c128*)A, (const c128*)Bop, (const c128*)C, (const c128*)psi, B, N, dt,
+                          ntau, (c128*)corr, st);
+  }
+  note_path("tdse_pair_rows");
+  constexpr int CHUNK = 32767;   // 2 CHUNK states fill the grid's y extent
+  for (int b0 = 0; b0 < B; b0 += CHUNK) {
+    QD_TRY(tdse_pair_rows((const c128*)H, (const c128*)A, (const c128*)Bop, (const c128*)C,
+                          (const c128*)psi + (size_t)b0 * N, std::min(CHUNK, B - b0), N, dt, ntau,
+                          (c128*)corr + (size_t)b0 * ntau, st));
+  }
+  return QD_OK;
 }
 
 extern "C" int qd_tdse_driven_rk4(const qd_c128* H0, const qd_c128* Hd, int nd, const qd_c128* fvals, qd_c128* psi,

@@ -63,6 +63,24 @@ def tdse_rk4(H, psi, dt, nsteps, save_every=0, e_ops=None):
     return snap, obs
 
 
+def tdse_pair_corr(H, A, Bop, C, psi, dt, ntau):
+    """Batched cross correlations on the GPU (qd_tdse_pair_corr): for every row psi_b the ket C psi_b and the bra
+    A^dagger psi_b are propagated by the RK4 of tdse_rk4 and corr[b, j] = <bra_b(j)| Bop |ket_b(j)> after j steps,
+    j = 0 .. ntau-1.  H, A, Bop, C [N,N], psi [B,N] (read only) torch complex128 on one device.  Returns corr
+    [B, ntau]."""
+    import torch
+    from . import _lib
+    dev = psi.device
+    _lib.ensure_device(dev)
+    B, N = psi.shape
+    corr = torch.empty((B, int(ntau)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_tdse_pair_corr(_lib.ptr(H), _lib.ptr(A), _lib.ptr(Bop), _lib.ptr(C), _lib.ptr(psi), B, N,
+                                           float(dt), int(ntau), _lib.ptr(corr), _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_tdse_pair_corr")
+    return corr
+
+
 def tdse_driven_rk4(H0, Hd, fvals, psi, dt, nout, e_ops=None):
     """Laser-driven batched RK4 on the GPU (qd_tdse_driven_rk4): block k of `nout` steps uses
     H0 - sum_d fvals[k, d] Hd[d].  H0 [N,N], Hd [nd,N,N] | None, fvals host complex [nblocks, nd],
@@ -221,12 +239,99 @@ def _quantum_dynamics(H, psi0, dt=0.001, Nt=1, e_ops=[], t0=0.0, nout=1, store_s
     return result
 
 
+def _check_corr_args(name, oplist, nops, **counts):
+    """Argument checks of the SESolver correlation functions, before any device work."""
+    if len(oplist) != nops:
+        raise ValueError(f"{name}: oplist must hold {nops} operators, got {len(oplist)}")
+    for k, v in counts.items():
+        if int(v) < 1:
+            raise ValueError(f"{name}: {k} must be >= 1, got {v}")
+
+
+def _propagator(H, dt, Nt):
+    """mol.py:1569-1600, rk4 branch: [I, I, R, R^2, ..., R^(Nt-1)] with R the one-step RK4 map (the reference appends
+    U before it steps, so the identity comes twice).  The columns of U are one tdse_rk4 batch of N wavefunctions
+    with a snapshot after every step."""
+    import torch
+    from ._util import default_device, to_numpy
+    if int(Nt) < 0:
+        raise ValueError(f"propagator: Nt must be >= 0, got {Nt}")
+    Hn = to_numpy(H, np.complex128)
+    N = Hn.shape[-1]
+    Ulist = [np.eye(N, dtype=complex)]
+    if Nt >= 1:
+        Ulist.append(np.eye(N, dtype=complex))
+    if Nt >= 2:
+        dev = default_device()
+        psi = torch.eye(N, dtype=torch.complex128, device=dev)
+        snap, _ = tdse_rk4(torch.from_numpy(np.ascontiguousarray(Hn)).to(dev), psi, dt, Nt - 1, save_every=1)
+        host = snap.cpu().numpy()   # [b, k, :] = R^(k+1) e_b: column b of R^(k+1)
+        Ulist += [np.ascontiguousarray(host[:, k, :].T) for k in range(Nt - 1)]
+    return Ulist
+
+
 class SESolver:
-    """Drop-in for pyqed.mol.SESolver (mol.py:1369-1459), time-independent H."""
+    """Drop-in for pyqed.mol.SESolver (mol.py:1369-1566), time-independent H."""
 
     def __init__(self, H=None):
         self.H = H
         self.groundstate = None
+
+    def propagator(self, dt, Nt):
+        """mol.py:1468-1470: list of Nt + 1 dense N x N arrays [I, I, R, ..., R^(Nt-1)]."""
+        return _propagator(self.H, dt, Nt)
+
+    def _corr_3op(self, psi_t, oplist, dt, ntau):
+        """corr [B, ntau] of the states psi_t [B, N] (device) for [a, b, c] = oplist: one qd_tdse_pair_corr."""
+        import torch
+        from ._util import to_numpy
+        dev = psi_t.device
+        N = psi_t.shape[1]
+        ops = []
+        for i, op in enumerate(oplist):
+            a = to_numpy(op, np.complex128)
+            if a.shape != (N, N):
+                raise ValueError(f"operator {i} has shape {a.shape}, expected {(N, N)}")
+            ops.append(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+        H = torch.from_numpy(np.ascontiguousarray(to_numpy(self.H, np.complex128))).to(dev)
+        return tdse_pair_corr(H, ops[0], ops[1], ops[2], psi_t, dt, ntau).cpu().numpy()
+
+    def correlation_3op_1t(self, psi0, oplist, dt, Nt):
+        """<A B(t) C> at t = 0 .. (Nt-1) dt (mol.py:1475-1501): complex ndarray (Nt,)."""
+        import torch
+        from ._util import default_device, to_numpy
+        _check_corr_args("correlation_3op_1t", oplist, 3, Nt=Nt)
+        p0 = to_numpy(psi0, np.complex128).reshape(1, -1)
+        psi = torch.from_numpy(np.ascontiguousarray(p0)).to(default_device())
+        return self._corr_3op(psi, oplist, dt, int(Nt))[0]
+
+    def correlation_3op_2t(self, psi0, oplist, dt, Nt, Ntau):
+        """<A(t) B(t+tau) C(t)> (mol.py:1503-1536): complex ndarray (Nt, Ntau), t_i = i dt, tau_j = j dt.  The Nt
+        states psi(t_i) come from one tdse_rk4 run and stay on the device; their 2 Nt kets and bras are one batch."""
+        import torch
+        from ._util import default_device, to_numpy
+        _check_corr_args("correlation_3op_2t", oplist, 3, Nt=Nt, Ntau=Ntau)
+        dev = default_device()
+        p0 = to_numpy(psi0, np.complex128).reshape(1, -1)
+        psi = torch.from_numpy(p0.copy()).to(dev)
+        psi_t = psi.clone()
+        if Nt > 1:
+            H = torch.from_numpy(np.ascontiguousarray(to_numpy(self.H, np.complex128))).to(dev)
+            snap, _ = tdse_rk4(H, psi, dt, int(Nt) - 1, save_every=1)
+            psi_t = torch.cat([psi_t, snap[0]], dim=0).contiguous()
+        return self._corr_3op(psi_t, oplist, dt, int(Ntau))
+
+    def correlation_4op_1t(self, psi0, oplist, dt=0.005, Nt=1):
+        """<A B(t) C(t) D> (mol.py:1538-1554): the 3-operator form with [a, b @ c, d]."""
+        _check_corr_args("correlation_4op_1t", oplist, 4, Nt=Nt)
+        a_op, b_op, c_op, d_op = oplist
+        return self.correlation_3op_1t(psi0, [a_op, b_op @ c_op, d_op], dt, Nt)
+
+    def correlation_4op_2t(self, psi0, oplist, dt=0.005, Nt=1, Ntau=1):
+        """<A(t) B(t+tau) C(t+tau) D(t)> (mol.py:1556-1566): the 3-operator form with [a, b @ c, d]."""
+        _check_corr_args("correlation_4op_2t", oplist, 4, Nt=Nt, Ntau=Ntau)
+        a_op, b_op, c_op, d_op = oplist
+        return self.correlation_3op_2t(psi0, [a_op, b_op @ c_op, d_op], dt, Nt, Ntau)
 
     def run(self, psi0=None, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, edip=None, pulse=None, use_sparse=True):
         """mol.py:1392-1459: time-independent H -> _quantum_dynamics; with a pulse (or a list of
