@@ -10,6 +10,7 @@
 //   (A tile row stride 18 complex: conflict-free ds_write_b128 staging and
 //    ds_read_b128 fragment reads; B tile stride BT: natural and conflict-free)
 //   LDS --(one complex = one ds_read_b128 per lane)--> MFMA fragments.
+// (The Lindblad batch kernel's GEMMs stage with global_load_lds instead and may use 3-product complex MACs: cg_dma_*.)
 // A complex 16x16x4 MAC is 4 real f64 MFMAs:
 //   Cr += Ar*Br ; Cr += (-Ai)*Bi ; Ci += Ar*Bi ; Ci += Ai*Br
 // f64 MFMA operand / result maps (cdna_hip_programming.md §3):
@@ -485,6 +486,246 @@ __device__ __forceinline__ void cg_herm_epilogue(const CgAcc<128>& acc, F&& f) {
         const int col = CgHermLayout::col0(wave, nj) + (lane & 15);
         f(row, col, cmk(acc.re[mi][nj][r], acc.im[mi][nj][r]));
       }
+}
+
+// ---------------------------------------------------------------- 128-block engine, direct global -> LDS staging
+// The Lindblad batch kernel's GEMMs (Y = C r on the CgCfg<128> tiles, X on the CgHermLayout tiles) with each K-tile
+// staged by 16-byte global_load_lds: no staging registers, no ds_write pass.  An LDS-DMA load writes lane-linearly
+// (wave base + lane * 16 B), so the A tile is [128 rows][16 k] without padding and the k index is XOR-ed with row & 15
+// on the per-lane SOURCE address and again in the fragment read: the 16 lanes of one ds_read_b128 group (rows r0 ..
+// r0 + 15, one k) hit 16 distinct 16-byte slots.  The B tile keeps the [16 k][128] image.  Tile t + 1's loads are
+// issued at the top of tile t into the other buffer; the __syncthreads() that ends a tile waits for them (vmcnt(0)).
+//
+// M3 > 0: the first M3 of a wave's 8 tiles (index mi * 4 + nj) use the 3-product complex MAC
+//   P1 += ar br ; P2 += ai bi ; P3 += (ar + ai)(br + bi) ;  re = P1 - P2, im = P3 - P1 - P2
+// (3 MFMAs per complex k-step for 4; P1 / P2 live in the tile's re / im registers until cg_dma_finalise).  M3 = 0 is
+// the 4-product arithmetic of cg_compute_tile / cg_herm_ksteps, bit for bit.
+#ifndef GLF_M3_TILES
+#define GLF_M3_TILES 8   // 3-product tiles per wave in the Lindblad batch kernel (0..8; 0 = 4-product arithmetic, A/B builds)
+#endif
+
+template <int M3>
+struct CgAcc3 : CgAcc<128> {
+  static_assert(M3 >= 0 && M3 <= 8, "3-product tiles per wave");
+  d4 p3[M3 > 0 ? M3 : 1];
+};
+
+typedef const __attribute__((address_space(1))) void cg_gvoid;
+typedef __attribute__((address_space(3))) void cg_lvoid;
+
+// A pointer every lane of the wave holds alike, as a scalar (the DMA loads then take an SGPR base + 32-bit lane offset).
+__device__ __forceinline__ const char* cg_uniform(const void* p) {
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
+}
+
+// Per-thread part of the staging addresses (bytes) and the wave's first element of each 512-element load round.
+struct CgDmaStage {
+  const CgSeg* segs;
+  int tps, lda, ldb;
+  unsigned offA, offB;
+  int wbase;
+  __device__ __forceinline__ CgDmaStage(const CgSeg* s, int tps_, int lda_, int ldb_) : segs(s), tps(tps_), lda(lda_), ldb(ldb_) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // staging address math stays per call (see cg_epilogue)
+    // A: element e = tid + 512 q sits at LDS slot (row e >> 4, k-slot e & 15) and holds A[row][(e & 15) ^ (row & 15)]
+    // (row & 15 = (tid >> 4) & 15 for every q);  B: element e -> B[e / 128][e % 128]
+    const int row = tid >> 4;
+    offA = (unsigned)(row * lda + ((tid & 15) ^ (row & 15))) * (unsigned)sizeof(c128);
+    offB = (unsigned)((tid >> 7) * ldb + (tid & 127)) * (unsigned)sizeof(c128);
+    wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
+  }
+  // K-tile t of the segment list -> LDS buffer buf (4 + 4 loads of 16 B per thread)
+  __device__ __forceinline__ void issue(int t, CgLds<128>& L, int buf) const {
+    const CgSeg sg = segs[t / tps];
+    const int kt = (t % tps) * CG_KT;
+    const char* ga = cg_uniform(sg.A + kt);
+    const char* gb = cg_uniform(sg.B + (size_t)kt * ldb);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(ga + (size_t)q * 32 * lda * sizeof(c128) + offA),
+                                       (cg_lvoid*)(&L.a[buf][wbase + CG_WG * q]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(gb + (size_t)q * 4 * ldb * sizeof(c128) + offB),
+                                       (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
+    }
+  }
+};
+
+// k-steps [Q0, Q1) of one K-tile for a wave with row tiles at r0[], column tiles at c0[] and the tiles SK skipped (the
+// Hermitian segments' tiles below the diagonal; 0 elsewhere).  The B fragments are read and consumed two at a time and
+// each operand sum is formed where its fragment is read: the 3-product tiles' third accumulator set takes the
+// registers that hold fragments in cg_herm_ksteps.
+template <int M3, unsigned SK, int Q0, int Q1>
+__device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAcc3<M3>& acc, const int (&r0)[2],
+                                              const int (&c0)[4]) {
+  constexpr int BT = 128, MW = 2, NW = 4;
+  constexpr unsigned M3MASK = (1u << M3) - 1u;           // tiles on the 3-product form
+  constexpr unsigned LIVE3 = M3MASK & ~SK;               // ... that this range computes
+  const int lane = threadIdx.x & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    const int kk = 4 * q;
+    c128 a[MW];
+    double sa[MW];
+#pragma unroll
+    for (int mi = 0; mi < MW; ++mi) {
+      a[mi] = L.a[buf][(r0[mi] + lr) * CG_KT + ((kk + lk) ^ lr)];
+      if ((LIVE3 >> (mi * 4)) & 15u) sa[mi] = a[mi].re + a[mi].im;
+    }
+#pragma unroll
+    for (int h = 0; h < NW; h += 2) {
+      c128 b[2];
+      double sb[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int nj = h + j;
+        if (((~SK >> nj) | (~SK >> (4 + nj))) & 1u) b[j] = L.b[buf][(kk + lk) * BT + c0[nj] + lr];
+        if (((LIVE3 >> nj) | (LIVE3 >> (4 + nj))) & 1u) sb[j] = b[j].re + b[j].im;
+      }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          const unsigned bit = 1u << (mi * 4 + nj);
+          if (SK & bit) continue;   // below the diagonal: no Hermitian part
+          acc.re[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].re, b[j].re, acc.re[mi][nj], 0, 0, 0);
+          if (!(M3MASK & bit))
+            acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].re, b[j].im, acc.im[mi][nj], 0, 0, 0);
+        }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          const unsigned bit = 1u << (mi * 4 + nj);
+          if (SK & bit) continue;
+          if (M3MASK & bit) {
+            acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].im, b[j].im, acc.im[mi][nj], 0, 0, 0);
+            acc.p3[mi * 4 + nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[j], acc.p3[mi * 4 + nj], 0, 0, 0);
+          } else {
+            acc.re[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[mi].im, b[j].im, acc.re[mi][nj], 0, 0, 0);
+            acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].im, b[j].re, acc.im[mi][nj], 0, 0, 0);
+          }
+        }
+    }
+  }
+}
+
+// The tiles of mask M scaled by the power of two S (exact): all three accumulator sets of a 3-product tile.
+template <int M3>
+__device__ __forceinline__ void cg_dma_scale(CgAcc3<M3>& acc, unsigned M, double S) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj)
+      if (M & (1u << (mi * 4 + nj))) {
+        acc.re[mi][nj] *= S;
+        acc.im[mi][nj] *= S;
+        if (mi * 4 + nj < M3) acc.p3[mi * 4 + nj] *= S;
+      }
+}
+
+template <int M3>
+__device__ __forceinline__ void cg_dma_zero(CgAcc3<M3>& acc) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      acc.re[mi][nj] = d4{0.0, 0.0, 0.0, 0.0};
+      acc.im[mi][nj] = d4{0.0, 0.0, 0.0, 0.0};
+      if (mi * 4 + nj < M3) acc.p3[mi * 4 + nj] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+}
+
+// (P1, P2, P3) -> (re, im) on the 3-product tiles; the accumulator then reads like a CgAcc<128>.
+template <int M3>
+__device__ __forceinline__ void cg_dma_finalise(CgAcc3<M3>& acc) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj)
+      if (mi * 4 + nj < M3) {
+        const d4 p1 = acc.re[mi][nj], p2 = acc.im[mi][nj];
+        acc.re[mi][nj] = p1 - p2;
+        acc.im[mi][nj] = (acc.p3[mi * 4 + nj] - p1) - p2;
+        // pinned tile by tile ahead of whatever follows the GEMM (the empty asm keeps the compiler from sinking the
+        // subtractions into the epilogue): each p3 dies here instead of staying live next to the epilogue's loads
+        asm volatile("" : "+v"(acc.re[mi][nj]), "+v"(acc.im[mi][nj]));
+      }
+}
+
+// sum_s A_s B_s over nseg segments of depth K (K % 16 == 0) on the CgCfg<128> tiles: cg_block_gemm<128> with the new
+// staging.  All threads call it; ends with a workgroup barrier.  Visit the result with cg_epilogue<128>.
+template <int M3>
+__device__ __forceinline__ void cg_dma_block_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
+                                                  CgAcc3<M3>& acc) {
+  constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
+  const int r0[2] = {wr0, wr0 + 16}, c0[4] = {wc0, wc0 + 16, wc0 + 32, wc0 + 48};
+  cg_dma_zero(acc);
+  const int tps = K / CG_KT, T = nseg * tps;
+  const CgDmaStage st(segs, tps, lda, ldb);
+  st.issue(0, L, 0);
+  __syncthreads();
+  for (int t = 0; t < T; ++t) {
+    if (t + 1 < T) st.issue(t + 1, L, (t + 1) & 1);
+    cg_sched_fence();
+    cg_dma_ksteps<M3, 0u, 0, NQ>(L, t & 1, acc, r0, c0);
+    __syncthreads();
+  }
+  cg_dma_finalise(acc);
+}
+
+// K-tiles [t0, t1) of the X GEMM (of T in all) for wave W with the skipped tiles SK fixed at compile time.
+template <int M3, int W, unsigned SK>
+__device__ __forceinline__ void cg_dma_herm_x_range(int t0, int t1, int T, const CgDmaStage& st, CgLds<128>& L,
+                                                    CgAcc3<M3>& acc) {
+  constexpr int NQ = CG_KT / 4, R0 = 16 * (W >> 1), R1 = 16 * (7 - (W >> 1));
+  const int r0[2] = {R0, R1};
+  const int c0[4] = {16 * cg_herm_ctile(W, 0), 16 * cg_herm_ctile(W, 1), 16 * cg_herm_ctile(W, 2),
+                     16 * cg_herm_ctile(W, 3)};
+  for (int t = t0; t < t1; ++t) {
+    if (t + 1 < T) st.issue(t + 1, L, (t + 1) & 1);
+    cg_sched_fence();
+    cg_dma_ksteps<M3, SK, 0, NQ>(L, t & 1, acc, r0, c0);
+    __syncthreads();
+  }
+}
+
+// cg_herm_x_gemm (same segments, tile layout and roles; segs[0] plain, segs[1..] Hermitian) with the new staging.
+// All threads call it; ends with a workgroup barrier.  Visit the result with cg_herm_epilogue / herm_k_pass.
+template <int M3>
+__device__ __forceinline__ void cg_dma_herm_x_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
+                                                   CgAcc3<M3>& acc) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  cg_dma_zero(acc);
+  const int tps = K / CG_KT, T = nseg * tps;
+  const CgDmaStage st(segs, tps, lda, ldb);
+  st.issue(0, L, 0);
+  __syncthreads();
+  auto run = [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    // the tiles above the diagonal take the Hermitian segments twice (cg_herm_x_gemm doubles their A fragments):
+    // here their segment-0 sums are halved, the Hermitian segments run on the plain fragments and the result is
+    // doubled, 2 (A r / 2 + B W).  Powers of two commute with every rounding, so the bits are those of A r + 2 B W
+    // and no wave holds a second copy of its A fragments.
+    cg_dma_herm_x_range<M3, W, 0u>(0, tps, T, st, L, acc);
+    cg_dma_scale(acc, cg_herm_mask(W, false), 0.5);
+    cg_dma_herm_x_range<M3, W, cg_herm_mask(W, true)>(tps, T, T, st, L, acc);
+    cg_dma_scale(acc, cg_herm_mask(W, false), 2.0);
+  };
+#define QD_HT(w) \
+  case w: run(std::integral_constant<int, w>{}); break;
+  switch (wave) {
+    QD_HT(0) QD_HT(1) QD_HT(2) QD_HT(3) QD_HT(4) QD_HT(5) QD_HT(6) default: QD_HT(7)
+  }
+#undef QD_HT
+  cg_dma_finalise(acc);
 }
 
 // Quadrant layout (the Redfield GLF operands, no Hermitian segment; and the round-2 first version of the Lindblad

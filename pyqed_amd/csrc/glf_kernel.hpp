@@ -49,6 +49,13 @@ __host__ __device__ inline int glf_slots(int Np, int nc, int herm) {
   return (Np <= 128 ? 1 : 2) + nc;
 }
 
+// A double every lane holds alike, moved to scalar registers.
+__device__ __forceinline__ double wave_uniform(double v) {
+  const unsigned long long u = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+
 // Horner coefficient of RK4 stage m (0..3): s_{m+1} = rho + dt / (4 - m) L s_m  (see the file header)
 __device__ __forceinline__ double glf_horner_coef(double dt, int stage) { return rk4_horner_coef(dt, stage); }
 
@@ -81,7 +88,9 @@ __device__ __forceinline__ double glf_horner_coef(double dt, int stage) { return
 // Tr(E_m rho) = sum_ij rho_ij E_m[j][i] = sum_ij rho_ij eT_m[i][j]; fixed
 // reduction order (per-thread strided partials, wave butterfly, 8-wave sum).
 __device__ void wg_observables(const c128* rho, const c128* eT, int ne, size_t NN, c128* out, c128* sred) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));  // per call: the per-thread addresses are not kept in registers across a step's GEMMs
+  const int lane = tid & 63, wave = tid >> 6;
   for (int m = 0; m < ne; ++m) {
     const c128* e = eT + (size_t)m * NN;
     double sr = 0.0, si = 0.0;
@@ -134,6 +143,14 @@ __device__ __forceinline__ void split_block_gemm(const CgSeg* segs, int nseg, in
 }
 #ifndef GLF_HERM_PIPE
 #define GLF_HERM_PIPE false   // fragment double-buffering in the Hermitian kernel's GEMMs (A/B builds)
+#endif
+
+#ifndef GLF_DMA
+#define GLF_DMA 1   // Lindblad batch kernel <128, HERM, HSEG>: GEMM operands staged by global_load_lds (cg_dma_*; A/B: 0)
+#endif
+
+#ifndef GLF_M3_PRE_MAX
+#define GLF_M3_PRE_MAX 6   // more 3-product tiles than this: no GLF_EPI_PRE prefetch (its registers go to the accumulators)
 #endif
 
 #ifndef GLF_KW
@@ -212,7 +229,9 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
 
   const int nb = Np / BT;
   const double dt = p.dt;
-  CgAcc<BT> A;
+  // the Lindblad batch kernel's engine (direct global -> LDS staging, GLF_M3_TILES 3-product tiles per wave)
+  constexpr bool DMA = BT == 128 && HERM && HSEG && !CHUNK && GLF_HERM_X && GLF_DMA;
+  std::conditional_t<DMA, CgAcc3<GLF_M3_TILES>, CgAcc<BT>> A;
   QD_TIMING_DECL
 
   for (int step = 0; step < p.nsteps; ++step) {
@@ -220,7 +239,8 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
       // Horner stages (glf_horner_coef): rho -> s1 -> s2 -> s3 -> rho; single block: s_m in place in ws
       const c128* r = stage == 0 ? rho : ((stage - 1) & 1) ? rbuf1 : ws;
       c128* rn = stage == 3 ? rho : (stage & 1) ? rbuf1 : ws;
-      const double hc = glf_horner_coef(dt, stage);
+      double hc = glf_horner_coef(dt, stage);
+      if constexpr (DMA) hc = wave_uniform(hc);   // scalar registers: the four stages' coefficients stay out of the VGPRs
       auto rk4_update = [&](size_t idx, c128 k) { rn[idx] = cadd(rho[idx], cscale(k, hc)); };
       if constexpr (HERM) {
         // Hermitian rho: L[rho] = X + X^+ with X = (-iK) r + sum_c (C_c r)(C_c^+ / 2)   (single block, nb == 1;
@@ -231,7 +251,8 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             segs[0].B = r;
           }
           __syncthreads();
-          cg_block_gemm<BT, GLF_HERM_PIPE>(segs, 1, Np, Np, Np, L, A);
+          if constexpr (DMA) cg_dma_block_gemm(segs, 1, Np, Np, Np, L, A);
+          else cg_block_gemm<BT, GLF_HERM_PIPE>(segs, 1, Np, Np, Np, L, A);
           QD_TMARK(0);
           c128* Yc = Y + (size_t)c * NN;
           cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
@@ -251,7 +272,8 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             }
           }
           __syncthreads();
-          if constexpr (HX && HSEG) cg_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
+          if constexpr (DMA) cg_dma_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
+          else if constexpr (HX && HSEG) cg_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
           else if constexpr (HX) cg_herm_x_gemm_q(segs, 1 + nc, Np, Np, Np, L, A, false);
           else cg_block_gemm<BT, GLF_HERM_PIPE>(segs, 1 + nc, Np, Np, Np, L, A);
         } else {
@@ -304,9 +326,10 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
           };
           constexpr int NPER0 = (TS * TS + CG_WG - 1) / CG_WG;
           constexpr int CH0 = NPER0 < QD_EPI_CH ? NPER0 : QD_EPI_CH;
-          constexpr int NPRE = GLF_EPI_PRE < CH0 ? GLF_EPI_PRE : CH0;   // prefetched elements per thread
+          constexpr int EPRE = DMA && GLF_M3_TILES > GLF_M3_PRE_MAX ? 0 : GLF_EPI_PRE;
+          constexpr int NPRE = EPRE < CH0 ? EPRE : CH0;   // prefetched elements per thread
           c128 pre[NPRE ? NPRE : 1];
-          if constexpr (GLF_EPI_PRE) {   // round 0's first chunk (tile (0, 1): e -> (e / TS, TS + e % TS))
+          if constexpr (EPRE) {   // round 0's first chunk (tile (0, 1): e -> (e / TS, TS + e % TS))
 #pragma unroll
             for (int q = 0; q < NPRE; ++q) {
               const int e = tid + CG_WG * q;
@@ -467,7 +490,9 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
       if (s < p.nsave) {
         const int N = p.N;
         c128* out = p.snap + ((size_t)b * p.nsave + s) * N * N;
-        for (size_t i = threadIdx.x; i < (size_t)N * N; i += CG_WG) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));  // as in wg_observables
+        for (size_t i = tid; i < (size_t)N * N; i += CG_WG) {
           const int ii = (int)(i / N), jj = (int)(i % N);
           out[i] = rho[(size_t)ii * Np + jj];
         }
