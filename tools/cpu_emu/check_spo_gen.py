@@ -1,5 +1,9 @@
 """Host check of spo_gen.hip through the flat-loop emulation (tools/cpu_emu/libemu_spo.so) against oracle/spo.py.
-Debug tool: `python tools/cpu_emu/check_spo_gen.py` from the repo root after building libemu_spo.so."""
+Debug tool: from the repo root,
+    g++ -O1 -shared -fPIC -I tools/cpu_emu tools/cpu_emu/emu_spo.cpp -o tools/cpu_emu/libemu_spo.so
+    python tools/cpu_emu/check_spo_gen.py
+Each axis length picks its own plan (mixed radix, Bluestein, four-step, direct); tests/test_fft_engine_host.py runs the
+transforms alone through the same library."""
 import ctypes
 import os
 import sys
@@ -82,30 +86,27 @@ def check_1d(nx, nt=5, nout=2, B=2, seed=0):
 
 if __name__ == "__main__":
     worst = 0
-    for kind in ("0", "1", "2"):
-        os.environ["QD_SPO_FORCE_KIND"] = kind
-        cases = [((20, 20), 2), ((96, 80), 2), ((7, 11), 3), ((67, 5), 1), ((12, 10), 5), ((1, 9), 2)]
-        for dims, ns in cases:
-            e = check_nd(dims, ns)
-            print("kind", kind, "2d", dims, ns, e)
-            worst = max(worst, *e)
-        for dims, ns in [((24, 20, 18), 2), ((5, 6, 7), 3)]:
-            e = check_nd(dims, ns, nt=2)
-            print("kind", kind, "3d", dims, ns, e)
-            worst = max(worst, *e)
-        e = check_nd((20, 30), 2, nt=4, nout=2, merged=True)
-        print("kind", kind, "merged", e)
+    cases = [((20, 20), 2), ((96, 80), 2), ((7, 11), 3), ((67, 5), 1), ((12, 10), 5), ((1, 9), 2)]
+    for dims, ns in cases:
+        e = check_nd(dims, ns)
+        print("2d", dims, ns, e)
         worst = max(worst, *e)
-        e = check_nd((18, 14), 2, nt=4, nout=2, jacobi=True)
-        print("kind", kind, "jacobi", e)
+    for dims, ns in [((24, 20, 18), 2), ((5, 6, 7), 3)]:
+        e = check_nd(dims, ns, nt=2)
+        print("3d", dims, ns, e)
         worst = max(worst, *e)
-        for nx in (50, 97, 200, 127):
-            e = check_1d(nx)
-            print("kind", kind, "1d", nx, e)
-            worst = max(worst, e)
-    os.environ["QD_SPO_FORCE_KIND"] = "0"
+    e = check_nd((20, 30), 2, nt=4, nout=2, merged=True)
+    print("merged", e)
+    worst = max(worst, *e)
+    e = check_nd((18, 14), 2, nt=4, nout=2, jacobi=True)
+    print("jacobi", e)
+    worst = max(worst, *e)
+    for nx in (50, 97, 200, 127):
+        e = check_1d(nx)
+        print("1d", nx, e)
+        worst = max(worst, e)
     for nx in (2048, 6000, 2 * 2053):
         e = check_1d(nx, nt=3, nout=1, B=1)
-        print("auto 1d", nx, e)
+        print("1d", nx, e)
         worst = max(worst, e)
     print("WORST", worst)

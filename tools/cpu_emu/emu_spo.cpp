@@ -13,6 +13,8 @@ void set_error(const char* fmt, ...) {
 WsScope::WsScope(hipStream_t s) : st(s), mark(g_bufs.size()) {}
 WsScope::~WsScope() { while (g_bufs.size() > mark) { free(g_bufs.back()); g_bufs.pop_back(); } }
 int workspace(WsSlot, size_t bytes, void** ptr, hipStream_t) { *ptr = calloc(1, bytes + 16); g_bufs.push_back(*ptr); return 0; }
+void note_path(const char*) {}
+int copy_device(void* dst, const void* src, size_t n, hipStream_t) { memmove(dst, src, n); return 0; }
 }
 namespace qd { namespace spog { c128 sm[163840 / 16]; } }
 extern "C" {
@@ -24,5 +26,11 @@ int emu_spo_nd(void* psi, const void* Uh, const void* Uf, const void* K, const v
 int emu_spo1d(void* psi, const void* eV, const void* eVh, const void* eK, int nx, int B, int nt, int nout, void* snap) {
   return qd::spo1d_generic_run((qd::c128*)psi, (const qd::c128*)eV, (const qd::c128*)eVh, (const qd::c128*)eK, nx, B,
                                nt, nout, (qd::c128*)snap, nullptr);
+}
+// fft_lines on the [O][L][I] array x in place (call-scoped scratch as qd_fft_axis opens it); *l2 != 0: four-step slot
+// order, X[k] at (k % L1) * L2 + k / L1 with L1 = L / L2
+int emu_fft_lines(void* x, long O, int L, long I, int inv, int* l2) {
+  qd::WsScope wss_(nullptr);
+  return qd::fft_lines((qd::c128*)x, O, L, I, inv != 0, nullptr, l2);
 }
 }
