@@ -540,9 +540,12 @@ struct CgDmaStage {
   // K-tile t of the segment list -> LDS buffer buf (4 + 4 loads of 16 B per thread)
   __device__ __forceinline__ void issue(int t, CgLds<128>& L, int buf) const {
     const CgSeg sg = segs[t / tps];
-    const int kt = (t % tps) * CG_KT;
-    const char* ga = cg_uniform(sg.A + kt);
-    const char* gb = cg_uniform(sg.B + (size_t)kt * ldb);
+    issue_at(sg.A, sg.B, (t % tps) * CG_KT, L, buf);
+  }
+  // the K-tile at depth kt of the operand pair (A, B), named directly (no segment-table read)
+  __device__ __forceinline__ void issue_at(const c128* A, const c128* B, int kt, CgLds<128>& L, int buf) const {
+    const char* ga = cg_uniform(A + kt);
+    const char* gb = cg_uniform(B + (size_t)kt * ldb);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       __builtin_amdgcn_global_load_lds((cg_gvoid*)(ga + (size_t)q * 32 * lda * sizeof(c128) + offA),
@@ -681,6 +684,38 @@ __device__ __forceinline__ void cg_dma_block_gemm(const CgSeg* segs, int nseg, i
   cg_dma_finalise(acc);
 }
 
+// One link of a stage's K-tile stream (GLF_TILE_STREAM): A B of depth K on the CgCfg<128> tiles, the operands named
+// directly, with tile 0 of the GEMM that follows, (nA, nB), issued at the top of this GEMM's last K-tile into the
+// buffer that tile leaves free.  K / 16 must be even: the last tile then computes from buffer 1, buffer 0 was last read
+// one barrier earlier, and the follower finds its tile 0 where its own prologue would have put it.  The barrier that
+// ends the last tile waits for that load (vmcnt(0)), so the follower starts without issue(0) and without a prologue
+// barrier (cg_dma_block_gemm_stream with first = false, or cg_dma_herm_x_gemm with pre = true).  first: this GEMM
+// heads the stream and stages its own tile 0.  All threads call it; ends with a workgroup barrier.
+template <int M3>
+__device__ __forceinline__ void cg_dma_block_gemm_stream(const c128* A, const c128* B, const c128* nA, const c128* nB,
+                                                         bool first, int K, int lda, int ldb, CgLds<128>& L,
+                                                         CgAcc3<M3>& acc) {
+  constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
+  const int r0[2] = {wr0, wr0 + 16}, c0[4] = {wc0, wc0 + 16, wc0 + 32, wc0 + 48};
+  cg_dma_zero(acc);
+  const int T = K / CG_KT;
+  const CgDmaStage st(nullptr, T, lda, ldb);
+  if (first) {
+    st.issue_at(A, B, 0, L, 0);
+    __syncthreads();
+  }
+  for (int t = 0; t < T; ++t) {
+    if (t + 1 < T) st.issue_at(A, B, (t + 1) * CG_KT, L, (t + 1) & 1);
+    else st.issue_at(nA, nB, 0, L, 0);
+    cg_sched_fence();
+    cg_dma_ksteps<M3, 0u, 0, NQ>(L, t & 1, acc, r0, c0);
+    __syncthreads();
+  }
+  cg_dma_finalise(acc);
+}
+
 // K-tiles [t0, t1) of the X GEMM (of T in all) for wave W with the skipped tiles SK fixed at compile time.
 template <int M3, int W, unsigned SK>
 __device__ __forceinline__ void cg_dma_herm_x_range(int t0, int t1, int T, const CgDmaStage& st, CgLds<128>& L,
@@ -699,15 +734,18 @@ __device__ __forceinline__ void cg_dma_herm_x_range(int t0, int t1, int T, const
 
 // cg_herm_x_gemm (same segments, tile layout and roles; segs[0] plain, segs[1..] Hermitian) with the new staging.
 // All threads call it; ends with a workgroup barrier.  Visit the result with cg_herm_epilogue / herm_k_pass.
+// pre: tile 0 already sits in buffer 0, staged and waited for by the GEMM before it (cg_dma_block_gemm_stream).
 template <int M3>
 __device__ __forceinline__ void cg_dma_herm_x_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
-                                                   CgAcc3<M3>& acc) {
+                                                   CgAcc3<M3>& acc, bool pre = false) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   cg_dma_zero(acc);
   const int tps = K / CG_KT, T = nseg * tps;
   const CgDmaStage st(segs, tps, lda, ldb);
-  st.issue(0, L, 0);
-  __syncthreads();
+  if (!pre) {
+    st.issue(0, L, 0);
+    __syncthreads();
+  }
   auto run = [&](auto wc) {
     constexpr int W = decltype(wc)::value;
     // the tiles above the diagonal take the Hermitian segments twice (cg_herm_x_gemm doubles their A fragments):

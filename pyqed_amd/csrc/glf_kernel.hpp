@@ -149,6 +149,14 @@ __device__ __forceinline__ void split_block_gemm(const CgSeg* segs, int nseg, in
 #define GLF_DMA 1   // Lindblad batch kernel <128, HERM, HSEG>: GEMM operands staged by global_load_lds (cg_dma_*; A/B: 0)
 #endif
 
+// Stage-boundary levers of the Lindblad batch kernel (the DMA instantiation only; A/B: 0 each)
+#ifndef GLF_TILE_STREAM
+#define GLF_TILE_STREAM 1   // one K-tile stream per stage: each GEMM's last K-tile stages the next GEMM's tile 0
+#endif
+#ifndef GLF_RHO_PRE
+#define GLF_RHO_PRE 1   // Horner update: all of a thread's rho loads issued before the barrier that publishes pass B
+#endif
+
 #ifndef GLF_M3_PRE_MAX
 #define GLF_M3_PRE_MAX 6   // more 3-product tiles than this: no GLF_EPI_PRE prefetch (its registers go to the accumulators)
 #endif
@@ -245,6 +253,45 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
       if constexpr (HERM) {
         // Hermitian rho: L[rho] = X + X^+ with X = (-iK) r + sum_c (C_c r)(C_c^+ / 2)   (single block, nb == 1;
         // p.Cd holds C_c^+ / 2 on this path).  phase 1: Y_c = C_c r
+        constexpr bool STREAM = DMA && GLF_TILE_STREAM;
+        if constexpr (STREAM) {
+          // One K-tile stream per stage: Y_0 .. Y_{nc-1}, then X.  The X GEMM's segment table is written here, once;
+          // the Y GEMMs name their operands directly and never read it.  The last K-tile of each GEMM stages tile 0 of
+          // the next one (Y_{c+1}: (C_{c+1}, r); after the last c the X GEMM's (mK, r)), both known before the stage
+          // starts, so only the stage's first GEMM pays a cold tile.
+          // Invariants (keep ALL of these when editing):
+          //  (1) the table's first reader is the X GEMM's issue(1) at the top of its tile 0, at least Np / 16 tile-end
+          //      barriers after thread 0's writes (nc = 0: the barrier below); its last reader in the stage before is
+          //      separated from these writes by the barriers of the k passes;
+          //  (2) Np / 16 is even (Np = 128 here), so a GEMM's last tile reads buffer 1 and the lookahead goes to
+          //      buffer 0, last read one barrier earlier;
+          //  (3) no barrier follows the Y stores.  Every tile-end __syncthreads() of the X GEMM has an LDS-DMA load in
+          //      flight and is therefore s_waitcnt vmcnt(0) + s_barrier; vmcnt counts stores as well, so each wave's
+          //      Y stores are complete when it arrives at the barrier that ends X tile 0, and all of Y is complete and
+          //      workgroup-visible (one CU, write-through L1) once that barrier releases.  Segment 0 (tiles 0 ..
+          //      Np/16 - 1) reads (mK, r) only; the first load of a Y_c is issued at the top of tile Np/16 - 1, behind
+          //      the barrier that ends tile Np/16 - 2: six barriers later at Np = 128.  The Y stores drain under
+          //      segment 0's first MFMAs.  A GEMM loop whose tile-end barrier no longer drains vmcnt (counted waits, a
+          //      raw s_barrier) needs an explicit s_waitcnt vmcnt(0) ahead of one of segment 0's barriers.
+          //  (4) nothing between a lookahead and its consumer touches LDS buffer 0 (cg_epilogue stores from registers).
+          if (threadIdx.x == 0) {
+            segs[0].A = p.mK;
+            segs[0].B = r;
+            for (int c = 0; c < nc; ++c) {
+              segs[1 + c].A = Y + (size_t)c * NN;
+              segs[1 + c].B = p.Cd + (size_t)c * NN;
+            }
+          }
+          if (nc == 0) __syncthreads();   // no Y GEMM to hide the X prologue under
+          for (int c = 0; c < nc; ++c) {
+            const c128* nA = c + 1 < nc ? p.Cop + (size_t)(c + 1) * NN : p.mK;
+            cg_dma_block_gemm_stream(p.Cop + (size_t)c * NN, r, nA, r, c == 0, Np, Np, Np, L, A);
+            QD_TMARK(0);
+            c128* Yc = Y + (size_t)c * NN;
+            cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
+            QD_TMARK(1);
+          }
+        } else {
         for (int c = 0; c < nc; ++c) {
           if (threadIdx.x == 0) {
             segs[0].A = p.Cop + (size_t)c * NN;
@@ -259,10 +306,13 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
           QD_TMARK(1);
         }
         __syncthreads();
+        }
         // phase 2: X in registers (one accumulator over 1 + nc segments); k_ij = X_ij + conj(X_ji) is
         // formed from the accumulator and an LDS transpose: exactly Hermitian, fused RK4 epilogue
         constexpr bool HX = BT == 128 && GLF_HERM_X;   // tiles without the Hermitian part (cgemm_block.hpp)
-        if constexpr (!CHUNK) {
+        if constexpr (STREAM) {
+          cg_dma_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A, nc > 0);
+        } else if constexpr (!CHUNK) {
           if (threadIdx.x == 0) {
             segs[0].A = p.mK;
             segs[0].B = r;
@@ -326,7 +376,12 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
           };
           constexpr int NPER0 = (TS * TS + CG_WG - 1) / CG_WG;
           constexpr int CH0 = NPER0 < QD_EPI_CH ? NPER0 : QD_EPI_CH;
-          constexpr int EPRE = DMA && GLF_M3_TILES > GLF_M3_PRE_MAX ? 0 : GLF_EPI_PRE;
+          // RPRE: every rho element the thread updates (8 of tile (0, 1), 9 of the folded triangles) is loaded once its
+          // accumulator is dead, before the barrier that publishes pass B: one load latency per stage, most of it under
+          // that barrier, instead of one per chunk behind it.  At stage 3 (rn == rho) every element and its mirror are
+          // read and written by one thread, loads first.
+          constexpr bool RPRE = DMA && GLF_RHO_PRE;
+          constexpr int EPRE = (DMA && GLF_M3_TILES > GLF_M3_PRE_MAX) || RPRE ? 0 : GLF_EPI_PRE;
           constexpr int NPRE = EPRE < CH0 ? EPRE : CH0;   // prefetched elements per thread
           c128 pre[NPRE ? NPRE : 1];
           if constexpr (EPRE) {   // round 0's first chunk (tile (0, 1): e -> (e / TS, TS + e % TS))
@@ -336,35 +391,6 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
               if (e < TS * TS) pre[q] = rho[(e / TS) * Np + TS + e % TS];
             }
           }
-          if constexpr (HX && HSEG && GLF_KW) {
-            const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
-            auto pass = [&](auto pbc) {
-              constexpr bool PB = decltype(pbc)::value;
-#define QD_KW(w) \
-  case w: herm_k_pass<w, PB>(A, T01, Tt, lane, slot); break;
-              switch (wave) { QD_KW(0) QD_KW(1) QD_KW(2) QD_KW(3) QD_KW(4) QD_KW(5) QD_KW(6) default: QD_KW(7) }
-#undef QD_KW
-            };
-            pass(std::false_type{});
-            __syncthreads();
-            pass(std::true_type{});
-            __syncthreads();
-          } else {
-          visit([&](int row, int col, c128 v) {
-            const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
-            if (ti < tj) T01[ra * LD + cc] = v;
-            else if (ti == tj && ra < cc) Tt[ti * TRI + slot(ra, cc)] = v;
-            else if (ti == tj && ra == cc) Tt[ti * TRI + slot(ra, cc)] = cadd(v, cconj(v));
-          });
-          __syncthreads();
-          visit([&](int row, int col, c128 v) {
-            const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
-            c128* t = ti > tj ? &T01[cc * LD + ra] : (ti == tj && ra > cc) ? &Tt[ti * TRI + slot(cc, ra)] : nullptr;
-            if (t) *t = cadd(*t, cconj(v));
-          });
-          __syncthreads();
-          }
-          QD_TMARK(5);
           // round 0: tile (0, 1), element e -> (e / TS, TS + e % TS), k at T01; round 1: the two folded diagonal
           // triangles, element e -> k at Tt[e]
           auto place_rd = [&](auto rdc, int e, int& gi, int& gj) -> const c128* {
@@ -381,6 +407,55 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             gj = ts * TS + (lo ? u + v : ra + v - (TS - u));
             return &Tt[e];
           };
+          constexpr int NP0 = TS * TS / CG_WG, NP1 = (2 * TRI + CG_WG - 1) / CG_WG;
+          static_assert(!RPRE || TS * TS % CG_WG == 0, "tile (0, 1) in whole rounds of the workgroup");
+          c128 q0[RPRE ? NP0 : 1], q1[RPRE ? NP1 : 1];
+          auto rho_prefetch = [&]() {
+            if constexpr (RPRE) {
+#pragma unroll
+              for (int q = 0; q < NP0; ++q) {
+                const int e = tid + CG_WG * q;
+                q0[q] = rho[(e / TS) * Np + TS + e % TS];
+              }
+#pragma unroll
+              for (int q = 0; q < NP1; ++q) {   // the last round is partial: clamped, so that no load sits in a branch
+                int gi, gj;
+                place_rd(std::integral_constant<int, 1>{}, min(tid + CG_WG * q, 2 * TRI - 1), gi, gj);
+                q1[q] = rho[gi * Np + gj];
+              }
+            }
+          };
+          if constexpr (HX && HSEG && GLF_KW) {
+            const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
+            auto pass = [&](auto pbc) {
+              constexpr bool PB = decltype(pbc)::value;
+#define QD_KW(w) \
+  case w: herm_k_pass<w, PB>(A, T01, Tt, lane, slot); break;
+              switch (wave) { QD_KW(0) QD_KW(1) QD_KW(2) QD_KW(3) QD_KW(4) QD_KW(5) QD_KW(6) default: QD_KW(7) }
+#undef QD_KW
+            };
+            pass(std::false_type{});
+            __syncthreads();
+            pass(std::true_type{});
+            rho_prefetch();
+            __syncthreads();
+          } else {
+          visit([&](int row, int col, c128 v) {
+            const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
+            if (ti < tj) T01[ra * LD + cc] = v;
+            else if (ti == tj && ra < cc) Tt[ti * TRI + slot(ra, cc)] = v;
+            else if (ti == tj && ra == cc) Tt[ti * TRI + slot(ra, cc)] = cadd(v, cconj(v));
+          });
+          __syncthreads();
+          visit([&](int row, int col, c128 v) {
+            const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
+            c128* t = ti > tj ? &T01[cc * LD + ra] : (ti == tj && ra > cc) ? &Tt[ti * TRI + slot(cc, ra)] : nullptr;
+            if (t) *t = cadd(*t, cconj(v));
+          });
+          rho_prefetch();
+          __syncthreads();
+          }
+          QD_TMARK(5);
           // Horner update of one upper element (i, j) with k, writing the mirror (j, i) as the conjugate
           auto update = [&](int gi, int gj, c128 k, c128 r0v) {
             const int id = gi * Np + gj, mid = gj * Np + gi;
@@ -392,23 +467,26 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             constexpr int rd = decltype(rdc)::value;
             constexpr int NE = rd == 0 ? TS * TS : 2 * TRI;
             constexpr int NPER = (NE + CG_WG - 1) / CG_WG;
-            constexpr int CH = NPER < QD_EPI_CH ? NPER : QD_EPI_CH;
-            for (int q0 = 0; q0 < NPER; q0 += CH) {
+            constexpr int CH = RPRE || NPER < QD_EPI_CH ? NPER : QD_EPI_CH;   // RPRE: one chunk, loaded already
+            for (int qb = 0; qb < NPER; qb += CH) {
               c128 r0[CH];
 #pragma unroll
               for (int q = 0; q < CH; ++q) {
-                const int e = tid + CG_WG * (q0 + q);
-                if (q0 + q < NPER && (NE % CG_WG == 0 || e < NE)) {
+                const int e = tid + CG_WG * (qb + q);
+                if constexpr (RPRE) {
+                  if constexpr (rd == 0) r0[q] = q0[q];
+                  else r0[q] = q1[q];
+                } else if (qb + q < NPER && (NE % CG_WG == 0 || e < NE)) {
                   int gi, gj;
                   place_rd(rdc, e, gi, gj);
-                  if (NPRE && rd == 0 && q0 == 0 && q < NPRE) r0[q] = pre[q < NPRE ? q : 0];
+                  if (NPRE && rd == 0 && qb == 0 && q < NPRE) r0[q] = pre[q < NPRE ? q : 0];
                   else r0[q] = rho[gi * Np + gj];
                 }
               }
 #pragma unroll
               for (int q = 0; q < CH; ++q) {
-                const int e = tid + CG_WG * (q0 + q);
-                if (q0 + q >= NPER || (NE % CG_WG != 0 && e >= NE)) continue;
+                const int e = tid + CG_WG * (qb + q);
+                if (qb + q >= NPER || (NE % CG_WG != 0 && e >= NE)) continue;
                 int gi, gj;
                 const c128 k = *place_rd(rdc, e, gi, gj);
                 update(gi, gj, k, r0[q]);
