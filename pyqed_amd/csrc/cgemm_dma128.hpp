@@ -1,0 +1,261 @@
+// cgemm_dma128.hpp — the Lindblad batch kernel's GEMM engine (glf_batch_kernel.hpp, its only user): 128-blocks staged
+// by 16-byte global_load_lds (no staging registers, no ds_write pass), 3-product complex MACs.
+// An LDS-DMA load writes lane-linearly (wave base + lane * 16 B), so the A tile is [128 rows][16 k] without padding and
+// the k index is XOR-ed with row & 15 on the per-lane SOURCE address and again in the fragment read: the 16 lanes of one
+// ds_read_b128 group (rows r0 .. r0 + 15, one k) hit 16 distinct 16-byte slots.  The B tile keeps the [16 k][128] image.
+// Tile t + 1's loads are issued at the top of tile t into the other buffer; the __syncthreads() that ends a tile waits
+// for them (vmcnt(0)).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
+//   P1 += ar br ; P2 += ai bi ; P3 += (ar + ai)(br + bi) ;  re = P1 - P2, im = P3 - P1 - P2
+// with P1 / P2 in the tile's re / im registers until cg_dma_finalise.
+// Hermitian X GEMM: X = A r + sum_c B_c W_c (segment 0; segments >= 1, W = C^+ / 2) for k = X + X^+.  Only k on the
+// upper triangle is used and B W (= C r C^+ / 2) is itself Hermitian, so the segments >= 1 skip the 16 x 16 tiles below
+// the diagonal (there X = A r alone) and each tile above it takes the full C r C^+ instead of its half:
+// k_ij = (A r)_ij + conj((A r)_ji) + (C r C^+)_ij for i < j; diagonal tiles keep the half in both triangles.  Tile
+// layout (16-tiles R, C in 0..7): wave w = 2 i + h owns row tiles {i, 7 - i} and the column tiles cg_herm_ctile(w, .),
+// placed so that each SIMD's two waves (w, w + 4) hold 9 of the 36 tiles with R <= C.
+#pragma once
+#include "cgemm_block.hpp"
+
+namespace qd {
+
+// Column tile nj of wave w, and the wave's tiles (bit mi * 4 + nj) below the diagonal (skipped in the Hermitian
+// segments) / above it (which take those segments twice).
+constexpr int cg_herm_ctile(int w, int nj) {
+  constexpr unsigned short cols[8] = {0x3210, 0x7654, 0x7610, 0x5432, 0x7432, 0x6510, 0x5410, 0x7632};
+  return (cols[w] >> (nj * 4)) & 15;
+}
+constexpr unsigned cg_herm_mask(int w, bool below) {
+  unsigned m = 0;
+  for (int mi = 0; mi < 2; ++mi)
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (w >> 1) : 7 - (w >> 1), C = cg_herm_ctile(w, nj);
+      if (below ? R > C : R < C) m |= 1u << (mi * 4 + nj);
+    }
+  return m;
+}
+
+// CgAcc<128> with the third accumulator set of the 3-product form (tile index mi * 4 + nj)
+struct CgAcc3 : CgAcc<128> { d4 p3[8]; };
+
+typedef const __attribute__((address_space(1))) void cg_gvoid;
+typedef __attribute__((address_space(3))) void cg_lvoid;
+
+// A pointer every lane of the wave holds alike, as a scalar (the DMA loads then take an SGPR base + 32-bit lane offset).
+__device__ __forceinline__ const char* cg_uniform(const void* p) {
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
+}
+
+// Per-thread part of the staging addresses (bytes) and the wave's first element of each 512-element load round.
+struct CgDmaStage {
+  const CgSeg* segs;
+  int tps, lda, ldb;
+  unsigned offA, offB;
+  int wbase;
+  __device__ __forceinline__ CgDmaStage(const CgSeg* s, int tps_, int lda_, int ldb_) : segs(s), tps(tps_), lda(lda_), ldb(ldb_) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // staging address math stays per call (see cg_epilogue)
+    // A: element e = tid + 512 q sits at LDS slot (row e >> 4, k-slot e & 15) and holds A[row][(e & 15) ^ (row & 15)]
+    // (row & 15 = (tid >> 4) & 15 for every q);  B: element e -> B[e / 128][e % 128]
+    const int row = tid >> 4;
+    offA = (unsigned)(row * lda + ((tid & 15) ^ (row & 15))) * (unsigned)sizeof(c128);
+    offB = (unsigned)((tid >> 7) * ldb + (tid & 127)) * (unsigned)sizeof(c128);
+    wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
+  }
+  // K-tile t of the segment list -> LDS buffer buf (4 + 4 loads of 16 B per thread)
+  __device__ __forceinline__ void issue(int t, CgLds<128>& L, int buf) const {
+    const CgSeg sg = segs[t / tps];
+    issue_at(sg.A, sg.B, (t % tps) * CG_KT, L, buf);
+  }
+  // the K-tile at depth kt of the operand pair (A, B), named directly (no segment-table read)
+  __device__ __forceinline__ void issue_at(const c128* A, const c128* B, int kt, CgLds<128>& L, int buf) const {
+    const char* ga = cg_uniform(A + kt);
+    const char* gb = cg_uniform(B + (size_t)kt * ldb);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(ga + (size_t)q * 32 * lda * sizeof(c128) + offA),
+                                       (cg_lvoid*)(&L.a[buf][wbase + CG_WG * q]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(gb + (size_t)q * 4 * ldb * sizeof(c128) + offB),
+                                       (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
+    }
+  }
+};
+
+// k-steps [Q0, Q1) of one K-tile for a wave with row tiles at r0[], column tiles at c0[] and the tiles SK skipped (the
+// Hermitian segments' tiles below the diagonal; 0 elsewhere).  The B fragments are read and consumed two at a time and
+// each operand sum is formed where its fragment is read: the third accumulator set takes the registers that a
+// 4-product k-step spends on holding all four B fragments at once.
+template <unsigned SK, int Q0, int Q1>
+__device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAcc3& acc, const int (&r0)[2],
+                                              const int (&c0)[4]) {
+  constexpr int BT = 128, MW = 2, NW = 4;
+  constexpr unsigned LIVE = 0xffu & ~SK;   // the tiles this range computes
+  const int lane = threadIdx.x & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    const int kk = 4 * q;
+    c128 a[MW];
+    double sa[MW];
+#pragma unroll
+    for (int mi = 0; mi < MW; ++mi) {
+      a[mi] = L.a[buf][(r0[mi] + lr) * CG_KT + ((kk + lk) ^ lr)];
+      if ((LIVE >> (mi * 4)) & 15u) sa[mi] = a[mi].re + a[mi].im;
+    }
+#pragma unroll
+    for (int h = 0; h < NW; h += 2) {
+      c128 b[2];
+      double sb[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int nj = h + j;
+        if (((LIVE >> nj) | (LIVE >> (4 + nj))) & 1u) {
+          b[j] = L.b[buf][(kk + lk) * BT + c0[nj] + lr];
+          sb[j] = b[j].re + b[j].im;
+        }
+      }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (SK & (1u << (mi * 4 + nj))) continue;   // below the diagonal: no Hermitian part
+          acc.re[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].re, b[j].re, acc.re[mi][nj], 0, 0, 0);
+        }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (SK & (1u << (mi * 4 + nj))) continue;
+          acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].im, b[j].im, acc.im[mi][nj], 0, 0, 0);
+          acc.p3[mi * 4 + nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[j], acc.p3[mi * 4 + nj], 0, 0, 0);
+        }
+    }
+  }
+}
+
+// The tiles of mask M scaled by the power of two S (exact): all three accumulator sets.
+__device__ __forceinline__ void cg_dma_scale(CgAcc3& acc, unsigned M, double S) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj)
+      if (M & (1u << (mi * 4 + nj))) {
+        acc.re[mi][nj] *= S;
+        acc.im[mi][nj] *= S;
+        acc.p3[mi * 4 + nj] *= S;
+      }
+}
+
+__device__ __forceinline__ void cg_dma_zero(CgAcc3& acc) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      acc.re[mi][nj] = d4{0.0, 0.0, 0.0, 0.0};
+      acc.im[mi][nj] = d4{0.0, 0.0, 0.0, 0.0};
+      acc.p3[mi * 4 + nj] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+}
+
+// (P1, P2, P3) -> (re, im); the accumulator then reads like a CgAcc<128>.
+__device__ __forceinline__ void cg_dma_finalise(CgAcc3& acc) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const d4 p1 = acc.re[mi][nj], p2 = acc.im[mi][nj];
+      acc.re[mi][nj] = p1 - p2;
+      acc.im[mi][nj] = (acc.p3[mi * 4 + nj] - p1) - p2;
+      // pinned tile by tile ahead of whatever follows the GEMM (the empty asm keeps the compiler from sinking the
+      // subtractions into the epilogue): each p3 dies here instead of staying live next to the epilogue's loads
+      asm volatile("" : "+v"(acc.re[mi][nj]), "+v"(acc.im[mi][nj]));
+    }
+}
+
+// One link of a stage's K-tile stream: A B of depth K on the CgCfg<128> tiles, the operands named directly, with
+// tile 0 of the GEMM that follows, (nA, nB), issued at the top of this GEMM's last K-tile into the buffer that tile
+// leaves free.  K / 16 must be even: the last tile then computes from buffer 1, buffer 0 was last read one barrier
+// earlier, and the follower finds its tile 0 where its own prologue would have put it.  The barrier that ends the last
+// tile waits for that load (vmcnt(0)), so the follower starts without issue(0) and without a prologue barrier
+// (cg_dma_block_gemm_stream with first = false, or cg_dma_herm_x_gemm with pre = true).  first: this GEMM heads the
+// stream and stages its own tile 0.  All threads call it; ends with a workgroup barrier.  Visit the result with
+// cg_epilogue<128>.
+__device__ __forceinline__ void cg_dma_block_gemm_stream(const c128* A, const c128* B, const c128* nA, const c128* nB,
+                                                         bool first, int K, int lda, int ldb, CgLds<128>& L,
+                                                         CgAcc3& acc) {
+  constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
+  const int r0[2] = {wr0, wr0 + 16}, c0[4] = {wc0, wc0 + 16, wc0 + 32, wc0 + 48};
+  cg_dma_zero(acc);
+  const int T = K / CG_KT;
+  const CgDmaStage st(nullptr, T, lda, ldb);
+  if (first) {
+    st.issue_at(A, B, 0, L, 0);
+    __syncthreads();
+  }
+  for (int t = 0; t < T; ++t) {
+    if (t + 1 < T) st.issue_at(A, B, (t + 1) * CG_KT, L, (t + 1) & 1);
+    else st.issue_at(nA, nB, 0, L, 0);
+    cg_sched_fence();
+    cg_dma_ksteps<0u, 0, NQ>(L, t & 1, acc, r0, c0);
+    __syncthreads();
+  }
+  cg_dma_finalise(acc);
+}
+
+// K-tiles [t0, t1) of the X GEMM (of T in all) for wave W with the skipped tiles SK fixed at compile time.
+template <int W, unsigned SK>
+__device__ __forceinline__ void cg_dma_herm_x_range(int t0, int t1, int T, const CgDmaStage& st, CgLds<128>& L,
+                                                    CgAcc3& acc) {
+  constexpr int NQ = CG_KT / 4, R0 = 16 * (W >> 1), R1 = 16 * (7 - (W >> 1));
+  const int r0[2] = {R0, R1};
+  const int c0[4] = {16 * cg_herm_ctile(W, 0), 16 * cg_herm_ctile(W, 1), 16 * cg_herm_ctile(W, 2),
+                     16 * cg_herm_ctile(W, 3)};
+  for (int t = t0; t < t1; ++t) {
+    if (t + 1 < T) st.issue(t + 1, L, (t + 1) & 1);
+    cg_sched_fence();
+    cg_dma_ksteps<SK, 0, NQ>(L, t & 1, acc, r0, c0);
+    __syncthreads();
+  }
+}
+
+// The Hermitian X GEMM of the file header (successor of the register-staged cg_herm_x_gemm: same segments, tile layout
+// and roles).  segs[0] = (A, r), segs[1..nseg-1] = (B_c, W_c) with sum_c B_c W_c Hermitian; K = the common depth
+// (tps = K / 16 K-tiles per segment).  Each wave runs the Hermitian segments on a code path of its own with compile-time
+// tile roles: no selects or branches in the MFMA stream.  All threads call it; ends with a workgroup barrier.
+// pre: tile 0 already sits in buffer 0, staged and waited for by the GEMM before it (cg_dma_block_gemm_stream).
+__device__ __forceinline__ void cg_dma_herm_x_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
+                                                   CgAcc3& acc, bool pre = false) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  cg_dma_zero(acc);
+  const int tps = K / CG_KT, T = nseg * tps;
+  const CgDmaStage st(segs, tps, lda, ldb);
+  if (!pre) {
+    st.issue(0, L, 0);
+    __syncthreads();
+  }
+  auto run = [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    // the tiles above the diagonal take the Hermitian segments twice: their segment-0 sums are halved, the Hermitian
+    // segments run on the plain fragments and the result is doubled, 2 (A r / 2 + B W).  Powers of two commute with
+    // every rounding, so the bits are those of A r + 2 B W and no wave holds a doubled copy of its A fragments.
+    cg_dma_herm_x_range<W, 0u>(0, tps, T, st, L, acc);
+    cg_dma_scale(acc, cg_herm_mask(W, false), 0.5);
+    cg_dma_herm_x_range<W, cg_herm_mask(W, true)>(tps, T, T, st, L, acc);
+    cg_dma_scale(acc, cg_herm_mask(W, false), 2.0);
+  };
+#define QD_HT(w) \
+  case w: run(std::integral_constant<int, w>{}); break;
+  switch (wave) {
+    QD_HT(0) QD_HT(1) QD_HT(2) QD_HT(3) QD_HT(4) QD_HT(5) QD_HT(6) default: QD_HT(7)
+  }
+#undef QD_HT
+  cg_dma_finalise(acc);
+}
+
+}  // namespace qd

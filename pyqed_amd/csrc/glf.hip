@@ -33,10 +33,11 @@
 // Matrices are zero-padded to Np = 32, 64 or a multiple of 128 so every GEMM
 // tile is full; the padding stays exactly zero through the propagation.
 // The complex GEMM engine's next-tile LDS stores issue before k-step 2 of 4 in this file's kernels (cgemm_block.hpp
-// default 3): with the Hermitian epilogue's round-0 loads issued before its LDS passes (GLF_EPI_PRE 4) and 8-element
-// Horner chunks, 351.5k -> 357.6k DM-steps/s on the headline batch (profiles/r06/lindblad/epilogue_knobs.txt)
+// default 3): with the register-staged Hermitian epilogue's round-0 loads issued before its LDS passes (EPI_PRE 4) and
+// 8-element Horner chunks, 351.5k -> 357.6k DM-steps/s on the then headline kernel (profiles/r06/lindblad/epilogue_knobs.txt)
 #define CG_STAGE_AT 2
 #include "glf_kernel.hpp"
+#include "glf_batch_kernel.hpp"   // lindblad_rk4_kernel<128, true, true, false>
 
 namespace qd {
 namespace {
@@ -225,6 +226,23 @@ __device__ __forceinline__ void slab_st(c128* p, c128 v) {
 __device__ __forceinline__ c128 slab_ld(const c128* p) {
   return cmk(__hip_atomic_load(&p->re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
              __hip_atomic_load(&p->im, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// The split-path GEMM engine: tile loads two K-tiles ahead of the MFMAs (cg_block_gemm_gen2; same MFMA order as one
+// tile ahead, bit-identical results).
+// (measured and rejected: 32-blocks with the even / odd K-tiles on the two wave halves of a single-buffered K-tile
+// pair, all eight waves issuing MFMAs: 64 matrices 204k vs 218-223k DM-steps/s, profiles/r03/lindblad/split_halves_ab.txt)
+template <int BT, typename APol, typename BPol>
+__device__ __forceinline__ void split_gemm(int T, APol& pa, BPol& pb, CgLds<BT>& L, CgAcc<BT>& acc) {
+  cg_block_gemm_gen2<BT>(T, pa, pb, L, acc);
+}
+template <int BT>
+__device__ __forceinline__ void split_block_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<BT>& L,
+                                                 CgAcc<BT>& acc) {
+  const int tps = K / CG_KT;
+  CgSegA<BT> pa{segs, tps, lda};
+  CgSegB<BT> pb{segs, tps, ldb};
+  split_gemm<BT>(nseg * tps, pa, pb, L, acc);
 }
 
 template <typename Pol>
@@ -566,19 +584,15 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   //    32-blocks; tools/glf_hsplit_sweep.sh: 198k / 233k / 258k / 264k DM-steps/s at 64 / 128 / 192 / 224 matrices
   //    against 82k / 164k / 242k / 278k for the persistent kernel);
   //  - else the persistent kernel (a workgroup per matrix).
-#ifndef GLF_HSPLIT_Y64
-#define GLF_HSPLIT_Y64 1
-#endif
+  constexpr bool HSPLIT_Y64 = true;   // the Hermitian pair path's Y launch on 64-blocks (below)
+  constexpr long SPLIT_MINWG = 512;   // workgroups per launch that a split-path block size must still give
   const int force = option(QD_OPT_GLF_PATH);
   int split_bt = 0;
   bool hsplit = false;
   {
-#ifndef GLF_SPLIT_MINWG
-#define GLF_SPLIT_MINWG 512
-#endif
     int bt = 32;
     for (int v : {128, 64}) {
-      if (v < Np && Np % v == 0 && (long)B * (Np / v) * (Np / v) >= GLF_SPLIT_MINWG) {
+      if (v < Np && Np % v == 0 && (long)B * (Np / v) * (Np / v) >= SPLIT_MINWG) {
         bt = v;
         break;
       }
@@ -598,7 +612,7 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   int ks = 1, ys = 1;
   // the Hermitian pair path's Y launch takes 64-blocks (all eight waves of a workgroup issuing MFMAs) from two per CU:
   // 128 matrices 288k -> 293k DM-steps/s, 64 matrices (one per CU) 255k -> 254k (profiles/r05/lindblad/y64_ab.txt)
-  const int y_bt = (hsplit && GLF_HSPLIT_Y64 && (long)B * (Np / 64) * (Np / 64) >= 512) ? 64 : split_bt;
+  const int y_bt = (hsplit && HSPLIT_Y64 && (long)B * (Np / 64) * (Np / 64) >= 512) ? 64 : split_bt;
   if (split_bt) {
     const long blocks = (long)B * (Np / split_bt) * (Np / split_bt);
     const long yblocks = (long)B * (Np / y_bt) * (Np / y_bt);
@@ -610,7 +624,7 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   const bool hk2 = hsplit;
   const int kslots = (ks > 1 ? ks : 0) + (hk2 ? 1 : 0);
   const size_t per = (size_t)(split_bt ? 2 + nc + kslots + (ys > 1 ? nc * ys : 0)
-                                       : glf_slots(Np, nc, herm)) * NN;
+                                       : glf_slots(Np, nc)) * NN;
   const size_t nticket = split_bt ? (size_t)B * (1 + nc) * (Np / std::min(split_bt, y_bt)) * (Np / std::min(split_bt, y_bt)) : 0;
   const size_t st_elems = (size_t)B * per + (pad ? (size_t)B * NN : 0) + (nticket + 3) / 4;
   void* wst = nullptr;

@@ -2,7 +2,8 @@
 // shared by glf.hip (every nc <= MAX_NC instantiation) and glf_chunk.hip (the CHUNK instantiations for longer
 // collapse-operator lists).  The CHUNK kernels live in their own translation unit: instantiated next to the
 // headline kernel they changed its register allocation (12 B per lane of scratch instead of 0).
-// See glf.hip for the algorithm.
+// This header holds the general kernel and the register-staged Hermitian kernel; the Lindblad batch kernel
+// <128, true, true, false> is an explicit specialization in glf_batch_kernel.hpp (glf.hip only).  Algorithm: glf.hip.
 #pragma once
 #include "cgemm_block.hpp"
 
@@ -26,7 +27,7 @@ struct LindbladParams {
   int step0, total_steps;  // this launch runs global steps step0 .. step0+nsteps-1 of total_steps
   int herm;                // Hermitian fast path (Lindblad, rho exactly Hermitian, single block)
   int hseg;                // Hermitian path: sum_c L_c r W_c is itself Hermitian (Lindblad C r C^+ / 2; not Redfield's
-                           // sum A r Lam^+), so its redundant tiles below the diagonal may be skipped (cg_herm_x_gemm)
+                           // sum A r Lam^+), so its redundant tiles below the diagonal may be skipped (cg_dma_herm_x_gemm)
   double dt;
   unsigned long long* tbuf;  // [B][8] per-phase wall-clock ticks (QD_PHASE_TIMING diagnostics) or null
   int stage, rin, rout;        // split path: RK4 stage; stage input / output buffer (0 = rho, 1/2 = scratch 0/1)
@@ -42,19 +43,8 @@ namespace {
 constexpr int MAX_NC = 256;  // collapse-operator / GLF pair segments held in the kernels' LDS segment tables (4 KB);
                              // longer lists run the persistent kernels' CHUNK instantiations (chunks of MAX_NC)
 
-
 // Per-matrix scratch slots of Np x Np: stage buffer(s), Y_c.
-__host__ __device__ inline int glf_slots(int Np, int nc, int herm) {
-  (void)herm;
-  return (Np <= 128 ? 1 : 2) + nc;
-}
-
-// A double every lane holds alike, moved to scalar registers.
-__device__ __forceinline__ double wave_uniform(double v) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
+__host__ __device__ inline int glf_slots(int Np, int nc) { return (Np <= 128 ? 1 : 2) + nc; }
 
 // Horner coefficient of RK4 stage m (0..3): s_{m+1} = rho + dt / (4 - m) L s_m  (see the file header)
 __device__ __forceinline__ double glf_horner_coef(double dt, int stage) { return rk4_horner_coef(dt, stage); }
@@ -115,106 +105,44 @@ __device__ void wg_observables(const c128* rho, const c128* eT, int ne, size_t N
   }
 }
 
-#ifndef GLF_HERM_X
-#define GLF_HERM_X 1   // Hermitian kernel at BT = 128: X GEMM on the CgHermLayout tiles (Lindblad: no Hermitian part below the diagonal; A/B: 0)
-#endif
-#ifndef GLF_EPI_PRE
-#define GLF_EPI_PRE 4   // Hermitian epilogue: this many rho loads of round 0's first chunk issued before the LDS passes
-#endif
-#ifndef GLF_SPLIT_DEPTH
-#define GLF_SPLIT_DEPTH 2   // split-path GEMMs: K-tiles of global loads in flight ahead of the MFMAs (1 or 2)
-#endif
-// the split-path GEMM engine: tile loads one (cg_block_gemm_gen) or two (cg_block_gemm_gen2) K-tiles ahead; same
-// MFMA order, bit-identical results
-// (measured and rejected: 32-blocks with the even / odd K-tiles on the two wave halves of a single-buffered K-tile
-// pair, all eight waves issuing MFMAs: 64 matrices 204k vs 218-223k DM-steps/s, profiles/r03/lindblad/split_halves_ab.txt)
-template <int BT, typename APol, typename BPol>
-__device__ __forceinline__ void split_gemm(int T, APol& pa, BPol& pb, CgLds<BT>& L, CgAcc<BT>& acc) {
-  if constexpr (GLF_SPLIT_DEPTH >= 2) cg_block_gemm_gen2<BT>(T, pa, pb, L, acc);
-  else cg_block_gemm_gen<BT>(T, pa, pb, L, acc);
-}
-template <int BT>
-__device__ __forceinline__ void split_block_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<BT>& L,
-                                                 CgAcc<BT>& acc) {
-  const int tps = K / CG_KT;
-  CgSegA<BT> pa{segs, tps, lda};
-  CgSegB<BT> pb{segs, tps, ldb};
-  split_gemm<BT>(nseg * tps, pa, pb, L, acc);
-}
-#ifndef GLF_HERM_PIPE
-#define GLF_HERM_PIPE false   // fragment double-buffering in the Hermitian kernel's GEMMs (A/B builds)
-#endif
-
-#ifndef GLF_DMA
-#define GLF_DMA 1   // Lindblad batch kernel <128, HERM, HSEG>: GEMM operands staged by global_load_lds (cg_dma_*; A/B: 0)
-#endif
-
-// Stage-boundary levers of the Lindblad batch kernel (the DMA instantiation only; A/B: 0 each)
-#ifndef GLF_TILE_STREAM
-#define GLF_TILE_STREAM 1   // one K-tile stream per stage: each GEMM's last K-tile stages the next GEMM's tile 0
-#endif
-#ifndef GLF_RHO_PRE
-#define GLF_RHO_PRE 1   // Horner update: all of a thread's rho loads issued before the barrier that publishes pass B
-#endif
-
-#ifndef GLF_M3_PRE_MAX
-#define GLF_M3_PRE_MAX 6   // more 3-product tiles than this: no GLF_EPI_PRE prefetch (its registers go to the accumulators)
-#endif
-
-#ifndef GLF_KW
-#define GLF_KW 1   // Hermitian kernel (HSEG): k = X + X^+ passes with the wave's tile roles as compile-time constants
-#endif
-
-// Pass A (PB = false) / pass B (PB = true) of k = X + X^+ into the LDS k buffers (see the kernel) for wave W of the
-// CgHermLayout tiles.  Tile (R, C) of 16 x 16 lies in 64 x 64 quadrant (R / 4, C / 4); only the diagonal 16 x 16 tiles
-// need per-element tests, every other tile is wholly upper (pass A stores), wholly lower (pass B adds the conjugate
-// at the mirror slot) or in the lower-left quadrant (pass B into T01 transposed).  Same stores / adds as the generic
-// visitor, without its per-element index arithmetic and branches.
-template <int W, bool PB, typename Slot>
-__device__ __forceinline__ void herm_k_pass(const CgAcc<128>& A, c128* T01, c128* Tt, int lane, Slot&& slot) {
-  constexpr int TS = 64, LD = TS + 1, TRI = TS * (TS + 1) / 2;
-  const int lr = lane >> 4, lc = lane & 15;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int nj = 0; nj < 4; ++nj) {
-      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);   // constants after unrolling
-      const int QR = R >> 2, QC = C >> 2, rr = (R & 3) * 16, c0 = (C & 3) * 16;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const c128 v = cmk(A.re[mi][nj][r], A.im[mi][nj][r]);
-        const int ra = rr + lr + 4 * r, cc = c0 + lc;
-        if (QR < QC) {
-          if (!PB) T01[ra * LD + cc] = v;
-        } else if (QR > QC) {
-          if (PB) {
-            c128* t = &T01[cc * LD + ra];
-            *t = cadd(*t, cconj(v));
-          }
-        } else if ((R & 3) < (C & 3)) {
-          if (!PB) Tt[QR * TRI + slot(ra, cc)] = v;
-        } else if ((R & 3) > (C & 3)) {
-          if (PB) {
-            c128* t = &Tt[QR * TRI + slot(cc, ra)];
-            *t = cadd(*t, cconj(v));
-          }
-        } else if (!PB) {
-          if (ra < cc) Tt[QR * TRI + slot(ra, cc)] = v;
-          else if (ra == cc) Tt[QR * TRI + slot(ra, cc)] = cadd(v, cconj(v));
-        } else if (ra > cc) {
-          c128* t = &Tt[QR * TRI + slot(cc, ra)];
-          *t = cadd(*t, cconj(v));
-        }
-      }
+// LDS k buffers of the Hermitian kernels (TS = BT / 2): T01 [TS][TS + 1] holds tile (0, 1) of k = X + X^+, Tt the upper
+// triangles of the two diagonal tiles, packed and folded (rows u and TS - 1 - u of a tile share one run of TS + 1 slots).
+template <int TS>
+struct HermK {
+  static constexpr int LD = TS + 1, TRI = TS * (TS + 1) / 2;
+  // folded packed slot of (ra, cc), ra <= cc, within a diagonal tile
+  static __device__ __forceinline__ int slot(int ra, int cc) {
+    const bool top = ra < TS / 2;
+    const int u = top ? ra : TS - 1 - ra;
+    return u * (TS + 1) + (top ? 0 : TS - u) + (cc - ra);
+  }
+  // Element e of update round RD: its place (gi, gj) in rho, returning where its k lies.  Round 0: tile (0, 1),
+  // e -> (e / TS, TS + e % TS), k in T01; round 1: the two folded diagonal triangles, k at Tt[e]
+  template <int RD>
+  static __device__ __forceinline__ const c128* place(const c128* T01, const c128* Tt, int e, int& gi, int& gj) {
+    if (RD == 0) {
+      gi = e / TS;
+      gj = TS + e % TS;
+      return &T01[gi * LD + e % TS];
     }
-}
+    const int ts = e / TRI, ff = e % TRI, u = ff / (TS + 1), v = ff % (TS + 1);
+    const bool lo = v < TS - u;
+    const int ra = lo ? u : TS - 1 - u;
+    gi = ts * TS + ra;
+    gj = ts * TS + (lo ? u + v : ra + v - (TS - u));
+    return &Tt[e];
+  }
+};
 
-// HSEG (Hermitian kernel only): sum_c L_c r W_c is itself Hermitian (Lindblad C r C^+ / 2), so the X GEMM skips its
-// tiles below the diagonal (cg_herm_x_gemm); without it (Redfield's GLF operands) the plain X GEMM (cg_herm_x_gemm_q).
+// HERM: rho exactly Hermitian (single block, Np == BT), L[rho] = X + X^+; else the general form.
+// HSEG (Hermitian, BT = 128, not CHUNK): sum_c L_c r W_c is itself Hermitian (Lindblad C r C^+ / 2), so the X GEMM
+// skips its tiles below the diagonal: the Lindblad batch kernel, a specialization of its own (glf_batch_kernel.hpp).
+// Without it (Redfield's GLF operands, the CHUNK kernels) the Hermitian kernel runs the plain X GEMM.
 // CHUNK (nc > MAX_NC only; the nc <= MAX_NC instantiations are compiled without it): the segment lists of the X / k
 // GEMMs run in chunks of MAX_NC collapse-operator segments through the LDS table, accumulating in registers.
 template <int BT, bool HERM, bool HSEG = false, bool CHUNK = false>
 __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
+  static_assert(!HSEG, "HSEG exists as <128, true, true, false> only: glf_batch_kernel.hpp, included by glf.hip");
   if (p.guard && __hip_atomic_load(p.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
   __shared__ CgLds<BT> L;
   __shared__ c128 sred[CG_WG / 64];
@@ -227,7 +155,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
   // single block (Np <= 128): every stage input is fully consumed by the GEMMs before the epilogue
   // overwrites it, so one stage buffer is updated in place; else two alternate.
   const bool single = (Np / BT) == 1;
-  c128* ws = p.ws + (size_t)b * glf_slots(Np, nc, HERM) * NN;
+  c128* ws = p.ws + (size_t)b * glf_slots(Np, nc) * NN;
   c128* rbuf1 = single ? ws : ws + NN;
   c128* Y = single ? ws + NN : ws + 2 * NN;
   c128* obs = p.obs ? p.obs + (size_t)b * (p.total_steps + 1) * p.ne : nullptr;
@@ -237,9 +165,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
 
   const int nb = Np / BT;
   const double dt = p.dt;
-  // the Lindblad batch kernel's engine (direct global -> LDS staging, GLF_M3_TILES 3-product tiles per wave)
-  constexpr bool DMA = BT == 128 && HERM && HSEG && !CHUNK && GLF_HERM_X && GLF_DMA;
-  std::conditional_t<DMA, CgAcc3<GLF_M3_TILES>, CgAcc<BT>> A;
+  CgAcc<BT> A;
   QD_TIMING_DECL
 
   for (int step = 0; step < p.nsteps; ++step) {
@@ -248,71 +174,27 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
       const c128* r = stage == 0 ? rho : ((stage - 1) & 1) ? rbuf1 : ws;
       c128* rn = stage == 3 ? rho : (stage & 1) ? rbuf1 : ws;
       double hc = glf_horner_coef(dt, stage);
-      if constexpr (DMA) hc = wave_uniform(hc);   // scalar registers: the four stages' coefficients stay out of the VGPRs
       auto rk4_update = [&](size_t idx, c128 k) { rn[idx] = cadd(rho[idx], cscale(k, hc)); };
       if constexpr (HERM) {
         // Hermitian rho: L[rho] = X + X^+ with X = (-iK) r + sum_c (C_c r)(C_c^+ / 2)   (single block, nb == 1;
         // p.Cd holds C_c^+ / 2 on this path).  phase 1: Y_c = C_c r
-        constexpr bool STREAM = DMA && GLF_TILE_STREAM;
-        if constexpr (STREAM) {
-          // One K-tile stream per stage: Y_0 .. Y_{nc-1}, then X.  The X GEMM's segment table is written here, once;
-          // the Y GEMMs name their operands directly and never read it.  The last K-tile of each GEMM stages tile 0 of
-          // the next one (Y_{c+1}: (C_{c+1}, r); after the last c the X GEMM's (mK, r)), both known before the stage
-          // starts, so only the stage's first GEMM pays a cold tile.
-          // Invariants (keep ALL of these when editing):
-          //  (1) the table's first reader is the X GEMM's issue(1) at the top of its tile 0, at least Np / 16 tile-end
-          //      barriers after thread 0's writes (nc = 0: the barrier below); its last reader in the stage before is
-          //      separated from these writes by the barriers of the k passes;
-          //  (2) Np / 16 is even (Np = 128 here), so a GEMM's last tile reads buffer 1 and the lookahead goes to
-          //      buffer 0, last read one barrier earlier;
-          //  (3) no barrier follows the Y stores.  Every tile-end __syncthreads() of the X GEMM has an LDS-DMA load in
-          //      flight and is therefore s_waitcnt vmcnt(0) + s_barrier; vmcnt counts stores as well, so each wave's
-          //      Y stores are complete when it arrives at the barrier that ends X tile 0, and all of Y is complete and
-          //      workgroup-visible (one CU, write-through L1) once that barrier releases.  Segment 0 (tiles 0 ..
-          //      Np/16 - 1) reads (mK, r) only; the first load of a Y_c is issued at the top of tile Np/16 - 1, behind
-          //      the barrier that ends tile Np/16 - 2: six barriers later at Np = 128.  The Y stores drain under
-          //      segment 0's first MFMAs.  A GEMM loop whose tile-end barrier no longer drains vmcnt (counted waits, a
-          //      raw s_barrier) needs an explicit s_waitcnt vmcnt(0) ahead of one of segment 0's barriers.
-          //  (4) nothing between a lookahead and its consumer touches LDS buffer 0 (cg_epilogue stores from registers).
-          if (threadIdx.x == 0) {
-            segs[0].A = p.mK;
-            segs[0].B = r;
-            for (int c = 0; c < nc; ++c) {
-              segs[1 + c].A = Y + (size_t)c * NN;
-              segs[1 + c].B = p.Cd + (size_t)c * NN;
-            }
-          }
-          if (nc == 0) __syncthreads();   // no Y GEMM to hide the X prologue under
-          for (int c = 0; c < nc; ++c) {
-            const c128* nA = c + 1 < nc ? p.Cop + (size_t)(c + 1) * NN : p.mK;
-            cg_dma_block_gemm_stream(p.Cop + (size_t)c * NN, r, nA, r, c == 0, Np, Np, Np, L, A);
-            QD_TMARK(0);
-            c128* Yc = Y + (size_t)c * NN;
-            cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
-            QD_TMARK(1);
-          }
-        } else {
         for (int c = 0; c < nc; ++c) {
           if (threadIdx.x == 0) {
             segs[0].A = p.Cop + (size_t)c * NN;
             segs[0].B = r;
           }
           __syncthreads();
-          if constexpr (DMA) cg_dma_block_gemm(segs, 1, Np, Np, Np, L, A);
-          else cg_block_gemm<BT, GLF_HERM_PIPE>(segs, 1, Np, Np, Np, L, A);
+          cg_block_gemm<BT>(segs, 1, Np, Np, Np, L, A);
           QD_TMARK(0);
           c128* Yc = Y + (size_t)c * NN;
           cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
           QD_TMARK(1);
         }
         __syncthreads();
-        }
         // phase 2: X in registers (one accumulator over 1 + nc segments); k_ij = X_ij + conj(X_ji) is
         // formed from the accumulator and an LDS transpose: exactly Hermitian, fused RK4 epilogue
-        constexpr bool HX = BT == 128 && GLF_HERM_X;   // tiles without the Hermitian part (cgemm_block.hpp)
-        if constexpr (STREAM) {
-          cg_dma_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A, nc > 0);
-        } else if constexpr (!CHUNK) {
+        constexpr bool QUAD = BT == 128;   // the X GEMM on the quadrant layout (cgemm_block.hpp)
+        if constexpr (!CHUNK) {
           if (threadIdx.x == 0) {
             segs[0].A = p.mK;
             segs[0].B = r;
@@ -322,10 +204,8 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             }
           }
           __syncthreads();
-          if constexpr (DMA) cg_dma_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
-          else if constexpr (HX && HSEG) cg_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
-          else if constexpr (HX) cg_herm_x_gemm_q(segs, 1 + nc, Np, Np, Np, L, A, false);
-          else cg_block_gemm<BT, GLF_HERM_PIPE>(segs, 1 + nc, Np, Np, Np, L, A);
+          if constexpr (QUAD) cg_quad_x_gemm(segs, 1 + nc, Np, Np, Np, L, A);
+          else cg_block_gemm<BT>(segs, 1 + nc, Np, Np, Np, L, A);
         } else {
           for (int c0 = 0; c0 < nc; c0 += MAX_NC) {   // (P r) + the first MAX_NC segments, then MAX_NC at a time
             const int first = c0 == 0 ? 1 : 0, cn = min(MAX_NC, nc - c0);
@@ -338,123 +218,55 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
               }
             }
             __syncthreads();
-            if constexpr (HX && HSEG) cg_herm_x_gemm(segs, first + cn, Np, Np, Np, L, A, first, first);
-            else if constexpr (HX) cg_herm_x_gemm_q(segs, first + cn, Np, Np, Np, L, A, false, first, first);
-            else cg_block_gemm<BT, GLF_HERM_PIPE>(segs, first + cn, Np, Np, Np, L, A, first);
+            if constexpr (QUAD) cg_quad_x_gemm(segs, first + cn, Np, Np, Np, L, A, first);
+            else cg_block_gemm<BT>(segs, first + cn, Np, Np, Np, L, A, first);
           }
         }
         auto visit = [&](auto&& f) {
-          if constexpr (HX && HSEG) cg_herm_epilogue(A, f);
-          else if constexpr (HX) cg_herm_epilogue_q(A, f);
+          if constexpr (QUAD) cg_quad_epilogue(A, f);
           else cg_epilogue<BT>(A, f);
         };
         QD_TMARK(2);
         // k = X + X^+ formed in LDS on the upper triangle only (TS = BT/2; the GEMM staging buffers are free).
         // Every stage quantity is exactly Hermitian (k_ji = conj(k_ij) bit for bit, and the RK4 updates are
         // elementwise with real coefficients), so each (i, j), i <= j, is computed once and its mirror written as
-        // the conjugate.  Pass A stores the accumulator's upper elements: tile (0, 1) into T01 [TS][TS + 1] and the
-        // diagonal tiles' upper triangles into Tt (packed, folded: rows u and TS - 1 - u of a tile share one run of
-        // TS + 1 slots); pass B adds the conjugate of every lower element at its mirror slot.  The accumulator
+        // the conjugate.  Pass A stores the accumulator's upper elements into the k buffers (HermK: T01, Tt);
+        // pass B adds the conjugate of every lower element at its mirror slot.  The accumulator
         // stays in registers through both passes (no global round trip of the diagonal tiles).  The Horner update then
         // reads rho on the upper triangle only and writes the next stage input (rho at stage 3) in full (the GEMMs,
         // observables and the caller read it).
         {
-          constexpr int TS = BT / 2, LD = TS + 1, TRI = TS * (TS + 1) / 2;
+          using KB = HermK<BT / 2>;
+          constexpr int TS = BT / 2, LD = KB::LD, TRI = KB::TRI;
           static_assert((TS * LD + 2 * TRI) * sizeof(c128) <= sizeof(CgLds<BT>), "LDS k buffers");
-#ifndef QD_EPI_CH
-#define QD_EPI_CH 8   // rho loads per thread in flight per chunk of the Horner update
-#endif
+          constexpr int EPI_PRE = 4;   // rho loads of round 0's first chunk issued before the LDS passes
+          constexpr int EPI_CH = 8;    // rho loads in flight per chunk of the Horner update (r06 epilogue_knobs.txt)
           c128* T01 = reinterpret_cast<c128*>(&L);
           c128* Tt = T01 + TS * LD;
           int tid = threadIdx.x;
           asm volatile("" : "+v"(tid));  // keep the per-element index math inside the stage loop (no LICM + spill)
-          // folded packed slot of (ra, cc), ra <= cc, within a diagonal tile
-          auto slot = [&](int ra, int cc) {
-            const bool top = ra < TS / 2;
-            const int u = top ? ra : TS - 1 - ra;
-            return u * (TS + 1) + (top ? 0 : TS - u) + (cc - ra);
-          };
           constexpr int NPER0 = (TS * TS + CG_WG - 1) / CG_WG;
-          constexpr int CH0 = NPER0 < QD_EPI_CH ? NPER0 : QD_EPI_CH;
-          // RPRE: every rho element the thread updates (8 of tile (0, 1), 9 of the folded triangles) is loaded once its
-          // accumulator is dead, before the barrier that publishes pass B: one load latency per stage, most of it under
-          // that barrier, instead of one per chunk behind it.  At stage 3 (rn == rho) every element and its mirror are
-          // read and written by one thread, loads first.
-          constexpr bool RPRE = DMA && GLF_RHO_PRE;
-          constexpr int EPRE = (DMA && GLF_M3_TILES > GLF_M3_PRE_MAX) || RPRE ? 0 : GLF_EPI_PRE;
-          constexpr int NPRE = EPRE < CH0 ? EPRE : CH0;   // prefetched elements per thread
-          c128 pre[NPRE ? NPRE : 1];
-          if constexpr (EPRE) {   // round 0's first chunk (tile (0, 1): e -> (e / TS, TS + e % TS))
+          constexpr int CH0 = NPER0 < EPI_CH ? NPER0 : EPI_CH;
+          constexpr int NPRE = EPI_PRE < CH0 ? EPI_PRE : CH0;   // prefetched elements per thread
+          c128 pre[NPRE];
 #pragma unroll
-            for (int q = 0; q < NPRE; ++q) {
-              const int e = tid + CG_WG * q;
-              if (e < TS * TS) pre[q] = rho[(e / TS) * Np + TS + e % TS];
-            }
+          for (int q = 0; q < NPRE; ++q) {   // round 0's first chunk (tile (0, 1): e -> (e / TS, TS + e % TS))
+            const int e = tid + CG_WG * q;
+            if (e < TS * TS) pre[q] = rho[(e / TS) * Np + TS + e % TS];
           }
-          // round 0: tile (0, 1), element e -> (e / TS, TS + e % TS), k at T01; round 1: the two folded diagonal
-          // triangles, element e -> k at Tt[e]
-          auto place_rd = [&](auto rdc, int e, int& gi, int& gj) -> const c128* {
-            constexpr int rd = decltype(rdc)::value;
-            if (rd == 0) {
-              gi = e / TS;
-              gj = TS + e % TS;
-              return &T01[gi * LD + e % TS];
-            }
-            const int ts = e / TRI, ff = e % TRI, u = ff / (TS + 1), v = ff % (TS + 1);
-            const bool lo = v < TS - u;
-            const int ra = lo ? u : TS - 1 - u;
-            gi = ts * TS + ra;
-            gj = ts * TS + (lo ? u + v : ra + v - (TS - u));
-            return &Tt[e];
-          };
-          constexpr int NP0 = TS * TS / CG_WG, NP1 = (2 * TRI + CG_WG - 1) / CG_WG;
-          static_assert(!RPRE || TS * TS % CG_WG == 0, "tile (0, 1) in whole rounds of the workgroup");
-          c128 q0[RPRE ? NP0 : 1], q1[RPRE ? NP1 : 1];
-          auto rho_prefetch = [&]() {
-            if constexpr (RPRE) {
-#pragma unroll
-              for (int q = 0; q < NP0; ++q) {
-                const int e = tid + CG_WG * q;
-                q0[q] = rho[(e / TS) * Np + TS + e % TS];
-              }
-#pragma unroll
-              for (int q = 0; q < NP1; ++q) {   // the last round is partial: clamped, so that no load sits in a branch
-                int gi, gj;
-                place_rd(std::integral_constant<int, 1>{}, min(tid + CG_WG * q, 2 * TRI - 1), gi, gj);
-                q1[q] = rho[gi * Np + gj];
-              }
-            }
-          };
-          if constexpr (HX && HSEG && GLF_KW) {
-            const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
-            auto pass = [&](auto pbc) {
-              constexpr bool PB = decltype(pbc)::value;
-#define QD_KW(w) \
-  case w: herm_k_pass<w, PB>(A, T01, Tt, lane, slot); break;
-              switch (wave) { QD_KW(0) QD_KW(1) QD_KW(2) QD_KW(3) QD_KW(4) QD_KW(5) QD_KW(6) default: QD_KW(7) }
-#undef QD_KW
-            };
-            pass(std::false_type{});
-            __syncthreads();
-            pass(std::true_type{});
-            rho_prefetch();
-            __syncthreads();
-          } else {
           visit([&](int row, int col, c128 v) {
             const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
             if (ti < tj) T01[ra * LD + cc] = v;
-            else if (ti == tj && ra < cc) Tt[ti * TRI + slot(ra, cc)] = v;
-            else if (ti == tj && ra == cc) Tt[ti * TRI + slot(ra, cc)] = cadd(v, cconj(v));
+            else if (ti == tj && ra < cc) Tt[ti * TRI + KB::slot(ra, cc)] = v;
+            else if (ti == tj && ra == cc) Tt[ti * TRI + KB::slot(ra, cc)] = cadd(v, cconj(v));
           });
           __syncthreads();
           visit([&](int row, int col, c128 v) {
             const int ti = row / TS, tj = col / TS, ra = row - ti * TS, cc = col - tj * TS;
-            c128* t = ti > tj ? &T01[cc * LD + ra] : (ti == tj && ra > cc) ? &Tt[ti * TRI + slot(cc, ra)] : nullptr;
+            c128* t = ti > tj ? &T01[cc * LD + ra] : (ti == tj && ra > cc) ? &Tt[ti * TRI + KB::slot(cc, ra)] : nullptr;
             if (t) *t = cadd(*t, cconj(v));
           });
-          rho_prefetch();
           __syncthreads();
-          }
           QD_TMARK(5);
           // Horner update of one upper element (i, j) with k, writing the mirror (j, i) as the conjugate
           auto update = [&](int gi, int gj, c128 k, c128 r0v) {
@@ -467,19 +279,16 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
             constexpr int rd = decltype(rdc)::value;
             constexpr int NE = rd == 0 ? TS * TS : 2 * TRI;
             constexpr int NPER = (NE + CG_WG - 1) / CG_WG;
-            constexpr int CH = RPRE || NPER < QD_EPI_CH ? NPER : QD_EPI_CH;   // RPRE: one chunk, loaded already
+            constexpr int CH = NPER < EPI_CH ? NPER : EPI_CH;
             for (int qb = 0; qb < NPER; qb += CH) {
               c128 r0[CH];
 #pragma unroll
               for (int q = 0; q < CH; ++q) {
                 const int e = tid + CG_WG * (qb + q);
-                if constexpr (RPRE) {
-                  if constexpr (rd == 0) r0[q] = q0[q];
-                  else r0[q] = q1[q];
-                } else if (qb + q < NPER && (NE % CG_WG == 0 || e < NE)) {
+                if (qb + q < NPER && (NE % CG_WG == 0 || e < NE)) {
                   int gi, gj;
-                  place_rd(rdc, e, gi, gj);
-                  if (NPRE && rd == 0 && qb == 0 && q < NPRE) r0[q] = pre[q < NPRE ? q : 0];
+                  KB::template place<rd>(T01, Tt, e, gi, gj);
+                  if (rd == 0 && qb == 0 && q < NPRE) r0[q] = pre[q < NPRE ? q : 0];
                   else r0[q] = rho[gi * Np + gj];
                 }
               }
@@ -488,7 +297,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
                 const int e = tid + CG_WG * (qb + q);
                 if (qb + q >= NPER || (NE % CG_WG != 0 && e >= NE)) continue;
                 int gi, gj;
-                const c128 k = *place_rd(rdc, e, gi, gj);
+                const c128 k = *KB::template place<rd>(T01, Tt, e, gi, gj);
                 update(gi, gj, k, r0[q]);
               }
             }
@@ -581,7 +390,6 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
   }
   QD_TIMING_FLUSH
 }
-
 
 }  // namespace
 }  // namespace qd
