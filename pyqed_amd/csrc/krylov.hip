@@ -69,7 +69,8 @@ __global__ __launch_bounds__(256) void hess_shift_kernel(const c128* __restrict_
   const c128 yk = cdiv(g, last);
   if (tid == 0 && res) {
     const c128 hk = H[(size_t)k * ldh + (k - 1)];
-    res[b] = sqrt(cabs2(cmul(hk, yk))) / beta;
+    const c128 hy = cmul(hk, yk);
+    res[b] = hypot(hy.re, hy.im) / beta;   // (the squares of a residual below 1e-154 would underflow to 0)
   }
   if (!Y) return;
   // back substitution, column by column: y_i = r_i / U_ii, then r_l -= U_li y_i for l < i
