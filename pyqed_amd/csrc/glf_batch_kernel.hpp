@@ -4,6 +4,12 @@
 // its register allocation sits on the 256-VGPR wall (0 spilled, 0 B scratch) and has changed with its neighbours in
 // the translation unit and with statements moved into helpers.  After any edit compare assembly and resource figures
 // with tools/isa_diff.py; a build that spills a VGPR or uses scratch is not a candidate.
+// What the allocator gives up first are loop invariants held across every K loop, so the kernel keeps none it can form
+// where it is used: the thread index, dt, n_c and Np each go through an empty asm at their point of use (the Horner
+// coefficient, the n_c tests, the epilogue's row offsets and the observables' lane index are then made per stage or
+// per call), and the epilogue's addresses are the matrix base in scalar registers plus one 32-bit offset.
+// Stage epilogue: k = X + X^+ is formed in the registers of the wave that owns the upper element, with one trip of the
+// lower elements through LDS and one barrier ahead of the Horner update (HermKL, herm_k_publish, herm_k_update).
 #pragma once
 #include "cgemm_dma128.hpp"
 #include "glf_kernel.hpp"
@@ -18,46 +24,155 @@ __device__ __forceinline__ double wave_uniform(double v) {
   return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
 
-// Pass A (PB = false) / pass B (PB = true) of k = X + X^+ into the LDS k buffers (see the kernel) for wave W of the
-// Hermitian tile layout (cgemm_dma128.hpp).  Tile (R, C) of 16 x 16 lies in 64 x 64 quadrant (R / 4, C / 4); only the
-// diagonal 16 x 16 tiles need per-element tests, every other tile is wholly upper (pass A stores), wholly lower (pass B
-// adds the conjugate at the mirror slot) or in the lower-left quadrant (pass B into T01 transposed).  The wave's tile
-// roles are compile-time constants: no per-element index arithmetic or branches.
-template <int W, bool PB, typename Slot>
-__device__ __forceinline__ void herm_k_pass(const CgAcc<128>& A, c128* T01, c128* Tt, int lane, Slot&& slot) {
-  constexpr int LD = HermK<64>::LD, TRI = HermK<64>::TRI;
+// wg_observables (glf_kernel.hpp) for this kernel: the same per-thread partials, wave butterfly and 8-wave sum, bit
+// for bit, with the butterfly's partner taken from the laundered thread index.  __shfl_xor's own lane id is hoisted
+// out of the step loop and then holds a VGPR across every K loop, and this kernel has none to spare.
+__device__ __forceinline__ double lane_xor(double v, int lane, int off) {
+  const int a = (lane ^ off) << 2;
+  const unsigned long long u = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_ds_bpermute(a, (int)(unsigned)u);
+  const unsigned hi = __builtin_amdgcn_ds_bpermute(a, (int)(unsigned)(u >> 32));
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ void wg_observables_batch(const c128* rho, const c128* eT, int ne, size_t NN, c128* out,
+                                                     c128* sred) {
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int m = 0; m < ne; ++m) {
+    const c128* e = eT + (size_t)m * NN;
+    double sr = 0.0, si = 0.0;
+    for (size_t i = tid; i < NN; i += CG_WG) {
+      c128 r = rho[i], x = e[i];
+      sr += r.re * x.re - r.im * x.im;
+      si += r.re * x.im + r.im * x.re;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      sr += lane_xor(sr, lane, off);
+      si += lane_xor(si, lane, off);
+    }
+    if (lane == 0) sred[wave] = cmk(sr, si);
+    __syncthreads();
+    if (tid == 0) {
+      c128 s = sred[0];
+      for (int w = 1; w < CG_WG / 64; ++w) s = cadd(s, sred[w]);
+      out[m] = s;
+    }
+    __syncthreads();
+  }
+}
+
+// Tiles whose rho a wave loads ahead of the publishing barrier.  A wave owns four or five tiles on and above the
+// diagonal: a fifth tile's rho is loaded behind the first tile's update, into the registers that tile frees (five
+// tiles' rho next to five tiles' accumulators spilled).
+constexpr int HERM_K_NPRE = 4;
+
+// The LDS image of conj(X) below the diagonal, stored at the mirror position: what the owner of an upper element
+// (i, j), i < j, adds to its own X_ij for k = X + X^+.  The 28 16 x 16 tiles above the diagonal take 256 slots each,
+// element (ra, cc) at ra * 16 + (cc ^ ra): the XOR spreads the writer's 16 lanes (one column, rows 16 B * 16 apart)
+// over 16 distinct 16-byte slots, and the reader's 16 lanes (one row) stay inside one 256-byte run.  The 8 diagonal
+// tiles take 128 slots each, rows ra and 15 - ra of the strict upper triangle folded into one run of 16: slot
+// 16 ra + cc for ra < 8, its complement in 255 for the rows below.
+struct HermKL {
+  static constexpr int DIAG0 = 28 * 256, SIZE = DIAG0 + 8 * 128;
+  static constexpr int tile(int R, int C) { return (R * 8 - R * (R + 1) / 2 + (C - R - 1)) * 256; }   // R < C
+  static __device__ __forceinline__ int slot(int ra, int cc) { return ra * 16 + (cc ^ ra); }
+  static __device__ __forceinline__ int dslot(int ra, int cc) {                                       // ra < cc
+    const int s = ra * 16 + cc;
+    return s ^ (ra < 8 ? 0 : 255);
+  }
+};
+
+// Wave W of the Hermitian tile layout (cgemm_dma128.hpp) publishes its accumulator elements below the diagonal into
+// the HermKL image: whole tiles with R > C (the lower-left quadrant among them) and the ra > cc elements of diagonal
+// tiles.  The wave's tile roles are compile-time constants: no per-element index arithmetic or branches outside the
+// diagonal tiles.  The accumulators of the tiles below the diagonal die here.
+template <int W>
+__device__ __forceinline__ void herm_k_publish(const CgAcc<128>& A, c128* KL, int lane) {
   const int lr = lane >> 4, lc = lane & 15;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
     for (int nj = 0; nj < 4; ++nj) {
       const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);   // constants after unrolling
-      const int QR = R >> 2, QC = C >> 2, rr = (R & 3) * 16, c0 = (C & 3) * 16;
+      if (R < C) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const c128 v = cmk(A.re[mi][nj][r], A.im[mi][nj][r]);
-        const int ra = rr + lr + 4 * r, cc = c0 + lc;
-        if (QR < QC) {
-          if (!PB) T01[ra * LD + cc] = v;
-        } else if (QR > QC) {
-          if (PB) {
-            c128* t = &T01[cc * LD + ra];
-            *t = cadd(*t, cconj(v));
-          }
-        } else if ((R & 3) < (C & 3)) {
-          if (!PB) Tt[QR * TRI + slot(ra, cc)] = v;
-        } else if ((R & 3) > (C & 3)) {
-          if (PB) {
-            c128* t = &Tt[QR * TRI + slot(cc, ra)];
-            *t = cadd(*t, cconj(v));
-          }
-        } else if (!PB) {
-          if (ra < cc) Tt[QR * TRI + slot(ra, cc)] = v;
-          else if (ra == cc) Tt[QR * TRI + slot(ra, cc)] = cadd(v, cconj(v));
-        } else if (ra > cc) {
-          c128* t = &Tt[QR * TRI + slot(cc, ra)];
-          *t = cadd(*t, cconj(v));
-        }
+        const int ra = lr + 4 * r;
+        if (R > C) KL[HermKL::tile(C, R) + HermKL::slot(lc, ra)] = cconj(v);
+        else if (ra > lc) KL[HermKL::DIAG0 + R * 128 + HermKL::dslot(lc, ra)] = cconj(v);
+      }
+    }
+}
+
+// rho on the elements of wave W's tiles on and above the diagonal, in MFMA layout (q[mi * 4 + nj][r]; the entries of
+// the tiles below the diagonal are never touched and take no registers).  Diagonal tiles load all 256 elements: no
+// load sits in a branch, the values below the diagonal are discarded.  Every address is the matrix's base (scalar
+// registers) plus a 32-bit byte offset, the lane's own plus a uniform one: no 64-bit address pair per element.
+template <int W>
+__device__ __forceinline__ void herm_k_rho_loads(const c128* rho, int Np, int lane, c128 (&q)[8][4], int N0, int N1) {
+  const unsigned vu = (unsigned)((lane >> 4) * Np + (lane & 15)) * (unsigned)sizeof(c128);
+  int n = 0;   // ordinal of the tile among the wave's tiles on and above the diagonal
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);
+      if (R > C) continue;
+      if (n < N0 || n >= N1) { ++n; continue; }
+      ++n;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned su = (unsigned)((16 * R + 4 * r) * Np) * (unsigned)sizeof(c128);   // uniform
+        q[mi * 4 + nj][r] = *reinterpret_cast<const c128*>(reinterpret_cast<const char*>(rho + 16 * C) + (vu + su));
+      }
+    }
+}
+
+// Behind the barrier that publishes the HermKL image: wave W reads the mirror's conjugate of each element of its
+// tiles on and above the diagonal (a tile's four reads first, straight-line), forms k = X_ij + conj(X_ji) (v + conj(v)
+// on the diagonal) and runs the Horner update rn_ij = rho_ij + hc k, writing the mirror rn_ji as the conjugate.
+// Addresses as in herm_k_rho_loads: uniform bases, one per-lane offset for the elements and one for the mirrors.
+template <int W, int NPRE>
+__device__ __forceinline__ void herm_k_update(const CgAcc<128>& A, const c128* KL, int lane, c128 (&q)[8][4],
+                                              const c128* rho, c128* rn, int Np, double hc) {
+  const int lr = lane >> 4, lc = lane & 15;
+  const unsigned vu = (unsigned)(lr * Np + lc) * (unsigned)sizeof(c128);
+  const unsigned vm = (unsigned)(lc * Np + lr) * (unsigned)sizeof(c128);
+  int n = 0;   // ordinal of the tile among the wave's tiles on and above the diagonal
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);
+      if (R > C) continue;
+      if (n >= 1) {   // rho of tile n - 1 + NPRE into the registers tile n - 1 has just freed, used NPRE - 1 tiles on
+        cg_sched_fence();
+        herm_k_rho_loads<W>(rho, Np, lane, q, n - 1 + NPRE, n + NPRE);
+        cg_sched_fence();
+      }
+      ++n;
+      c128 m[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ra = lr + 4 * r;
+        if (R < C) m[r] = KL[HermKL::tile(R, C) + HermKL::slot(ra, lc)];
+        else m[r] = KL[HermKL::DIAG0 + R * 128 + HermKL::dslot(ra, lc)];   // ra >= lc: some slot of the tile, discarded
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const c128 x = cmk(A.re[mi][nj][r], A.im[mi][nj][r]);
+        const int ra = lr + 4 * r;
+        const c128 k = cadd(x, R == C && ra == lc ? cconj(x) : m[r]);
+        const c128 v = cadd(q[mi * 4 + nj][r], cscale(k, hc));
+        const unsigned su = (unsigned)((16 * R + 4 * r) * Np) * (unsigned)sizeof(c128);   // uniform, as sm
+        const unsigned sm = (unsigned)(16 * C * Np) * (unsigned)sizeof(c128);
+        char* u = reinterpret_cast<char*>(rn + 16 * C) + (vu + su);
+        char* t = reinterpret_cast<char*>(rn + 16 * R + 4 * r) + (vm + sm);
+        if (R < C || ra <= lc) *reinterpret_cast<c128*>(u) = v;
+        if (R < C || ra < lc) *reinterpret_cast<c128*>(t) = cconj(v);
       }
     }
 }
@@ -71,17 +186,17 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel<128, true, true, fa
   __shared__ CgSeg segs[2 + MAX_NC];   // segment table in LDS (no scratch)
 
   const int b = blockIdx.x;
-  const int Np = p.Np, nc = p.nc;
+  const int Np = p.Np;
   const size_t NN = (size_t)Np * Np;
   c128* rho = p.rho + (size_t)b * NN;
   // single block: always true here (launched at Np == 128 only), tested at run time as in glf_kernel.hpp's template
   const bool single = (Np / BT) == 1;
-  c128* ws = p.ws + (size_t)b * glf_slots(Np, nc) * NN;
+  c128* ws = p.ws + (size_t)b * glf_slots(Np, p.nc) * NN;
   c128* rbuf1 = single ? ws : ws + NN;
   c128* Y = single ? ws + NN : ws + 2 * NN;
   c128* obs = p.obs ? p.obs + (size_t)b * (p.total_steps + 1) * p.ne : nullptr;
 
-  if (p.ne > 0 && p.step0 == 0) wg_observables(rho, p.eT, p.ne, NN, obs, sred);
+  if (p.ne > 0 && p.step0 == 0) wg_observables_batch(rho, p.eT, p.ne, NN, obs, sred);
   __syncthreads();
 
   const double dt = p.dt;
@@ -93,7 +208,11 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel<128, true, true, fa
       // Horner stages (glf_horner_coef): rho -> s1 -> s2 -> s3 -> rho; single block: s_m in place in ws
       const c128* r = stage == 0 ? rho : ((stage - 1) & 1) ? rbuf1 : ws;
       c128* rn = stage == 3 ? rho : (stage & 1) ? rbuf1 : ws;
-      const double hc = wave_uniform(glf_horner_coef(dt, stage));   // the stages' coefficients stay out of the VGPRs
+      // the stages' coefficients stay out of the VGPRs: formed per stage from a dt the compiler cannot see through
+      // (hoisted out of the step loop, dt / 3 and dt / 2 sat in four VGPRs across every K loop), then scalar
+      double dts = dt;
+      asm volatile("" : "+s"(dts));
+      const double hc = wave_uniform(glf_horner_coef(dts, stage));
       // Hermitian rho: L[rho] = X + X^+ with X = (-iK) r + sum_c (C_c r)(C_c^+ / 2)   (single block; p.Cd holds
       // C_c^+ / 2 on this path).  phase 1: Y_c = C_c r
       // One K-tile stream per stage: Y_0 .. Y_{nc-1}, then X.  The X GEMM's segment table is written here, once;
@@ -103,7 +222,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel<128, true, true, fa
       // Invariants (keep ALL of these when editing):
       //  (1) the table's first reader is the X GEMM's issue(1) at the top of its tile 0, at least Np / 16 tile-end
       //      barriers after thread 0's writes (nc = 0: the barrier below); its last reader in the stage before is
-      //      separated from these writes by the barriers of the k passes;
+      //      separated from these writes by the two barriers of the k epilogue;
       //  (2) Np / 16 is even (Np = 128 here), so a GEMM's last tile reads buffer 1 and the lookahead goes to
       //      buffer 0, last read one barrier earlier;
       //  (3) no barrier follows the Y stores.  Every tile-end __syncthreads() of the X GEMM has an LDS-DMA load in
@@ -115,7 +234,9 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel<128, true, true, fa
       //      segment 0's first MFMAs.  A GEMM loop whose tile-end barrier no longer drains vmcnt (counted waits, a
       //      raw s_barrier) needs an explicit s_waitcnt vmcnt(0) ahead of one of segment 0's barriers.
       //  (4) nothing between a lookahead and its consumer touches LDS buffer 0 (cg_epilogue stores from registers).
-      if (threadIdx.x == 0) {
+      int tid0 = threadIdx.x, nc = p.nc;
+      asm volatile("" : "+v"(tid0), "+s"(nc));   // tests made per stage: no flag register held across the K loops
+      if (tid0 == 0) {
         segs[0].A = p.mK;
         segs[0].B = r;
         for (int c = 0; c < nc; ++c) {
@@ -135,82 +256,42 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel<128, true, true, fa
       // phase 2: X in registers (one accumulator over 1 + nc segments), fused k and RK4 epilogue
       cg_dma_herm_x_gemm(segs, 1 + nc, Np, Np, Np, L, A, nc > 0);
       QD_TMARK(2);
-      // k = X + X^+ formed in the LDS k buffers on the upper triangle only, as in the register-staged Hermitian kernel
-      // (glf_kernel.hpp): pass A stores the accumulator's upper elements, pass B adds the conjugate of every lower one
-      // at its mirror slot (herm_k_pass); the Horner update reads rho on the upper triangle and writes both triangles.
+      // k = X + X^+ formed in the registers of the wave that owns the upper element: every wave publishes conj(X) of its
+      // elements below the diagonal at the mirror slot of the HermKL image (herm_k_publish; those accumulators die),
+      // loads rho on its tiles on and above the diagonal into the freed registers, and behind ONE barrier adds the
+      // mirror from LDS to its own X_ij and runs the Horner update on (i, j) and, as the conjugate, on (j, i)
+      // (herm_k_update).  Each k is the same two operands in the same addition as X_ij + conj(X_ji) formed in LDS.
+      // The rho loads sit before the barrier: one load latency per stage, most of it under the barrier.  At stage 3
+      // (rn == rho) every element and its mirror are read and written by one thread, loads first.  The closing barrier
+      // keeps the next stage's LDS-DMA out of the image and makes rn complete for it.
       {
-        using KB = HermK<BT / 2>;
-        constexpr int TS = BT / 2, LD = KB::LD, TRI = KB::TRI;
-        static_assert((TS * LD + 2 * TRI) * sizeof(c128) <= sizeof(CgLds<BT>), "LDS k buffers");
-        c128* T01 = reinterpret_cast<c128*>(&L);
-        c128* Tt = T01 + TS * LD;
+        static_assert(HermKL::SIZE * sizeof(c128) <= sizeof(CgLds<BT>), "LDS k image");
+        c128* KL = reinterpret_cast<c128*>(&L);
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));  // keep the per-element index math inside the stage loop (no LICM + spill)
-        auto slot = [&](int ra, int cc) { return KB::slot(ra, cc); };
-        // Every rho element the thread updates (8 of tile (0, 1), 9 of the folded triangles) is loaded once its
-        // accumulator is dead, before the barrier that publishes pass B: one load latency per stage, most of it under
-        // that barrier, instead of one per chunk behind it.  At stage 3 (rn == rho) every element and its mirror are
-        // read and written by one thread, loads first.
-        constexpr int NP0 = TS * TS / CG_WG, NP1 = (2 * TRI + CG_WG - 1) / CG_WG;
-        static_assert(TS * TS % CG_WG == 0, "tile (0, 1) in whole rounds of the workgroup");
-        c128 q0[NP0], q1[NP1];
-        auto rho_prefetch = [&]() {
-#pragma unroll
-          for (int q = 0; q < NP0; ++q) {
-            const int e = tid + CG_WG * q;
-            q0[q] = rho[(e / TS) * Np + TS + e % TS];
-          }
-#pragma unroll
-          for (int q = 0; q < NP1; ++q) {   // the last round is partial: clamped, so that no load sits in a branch
-            int gi, gj;
-            KB::place<1>(T01, Tt, min(tid + CG_WG * q, 2 * TRI - 1), gi, gj);
-            q1[q] = rho[gi * Np + gj];
-          }
-        };
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
-        auto pass = [&](auto pbc) {
-          constexpr bool PB = decltype(pbc)::value;
+        int Npe = Np;
+        asm volatile("" : "+s"(Npe));   // likewise the uniform row offsets: per stage, not in scalar registers for the run
+        auto tail = [&](auto wc) {
+          constexpr int W = decltype(wc)::value;
+          c128 q[8][4];
+          herm_k_publish<W>(A, KL, lane);
+          cg_sched_fence();   // the loads go into the registers the publishing frees: none may be scheduled ahead of it
+          herm_k_rho_loads<W>(rho, Npe, lane, q, 0, HERM_K_NPRE);
+          __syncthreads();
+          QD_TMARK(5);
+          herm_k_update<W, HERM_K_NPRE>(A, KL, lane, q, rho, rn, Npe, hc);
+        };
 #define QD_KW(w) \
-  case w: herm_k_pass<w, PB>(A, T01, Tt, lane, slot); break;
-          switch (wave) { QD_KW(0) QD_KW(1) QD_KW(2) QD_KW(3) QD_KW(4) QD_KW(5) QD_KW(6) default: QD_KW(7) }
+  case w: tail(std::integral_constant<int, w>{}); break;
+        switch (wave) { QD_KW(0) QD_KW(1) QD_KW(2) QD_KW(3) QD_KW(4) QD_KW(5) QD_KW(6) default: QD_KW(7) }
 #undef QD_KW
-        };
-        pass(std::false_type{});
-        __syncthreads();
-        pass(std::true_type{});
-        rho_prefetch();
-        __syncthreads();
-        QD_TMARK(5);
-        // Horner update of one upper element (i, j) with k, writing the mirror (j, i) as the conjugate; one chunk per
-        // round, its rho values loaded already
-        auto update = [&](int gi, int gj, c128 k, c128 r0v) {
-          const int id = gi * Np + gj, mid = gj * Np + gi;
-          const c128 v = cadd(r0v, cscale(k, hc));
-          rn[id] = v;
-          if (gi != gj) rn[mid] = cconj(v);
-        };
-        auto round = [&](auto rdc) {
-          constexpr int rd = decltype(rdc)::value;
-          constexpr int NE = rd == 0 ? TS * TS : 2 * TRI;
-          constexpr int NPER = (NE + CG_WG - 1) / CG_WG;
-#pragma unroll
-          for (int q = 0; q < NPER; ++q) {
-            const int e = tid + CG_WG * q;
-            if (NE % CG_WG != 0 && e >= NE) continue;
-            int gi, gj;
-            const c128 k = *KB::place<rd>(T01, Tt, e, gi, gj);
-            if constexpr (rd == 0) update(gi, gj, k, q0[q]);
-            else update(gi, gj, k, q1[q]);
-          }
-        };
-        round(std::integral_constant<int, 0>{});
-        round(std::integral_constant<int, 1>{});
         __syncthreads();
       }
       QD_TMARK(3);
     }
     const int gs = p.step0 + step + 1;  // global step count after this step
-    if (p.ne > 0) wg_observables(rho, p.eT, p.ne, NN, obs + (size_t)gs * p.ne, sred);
+    if (p.ne > 0) wg_observables_batch(rho, p.eT, p.ne, NN, obs + (size_t)gs * p.ne, sred);
     if (p.snap && p.save_every > 0 && (gs % p.save_every) == 0) {
       const int s = gs / p.save_every - 1;
       if (s < p.nsave) {
