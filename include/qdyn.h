@@ -278,6 +278,47 @@ int qd_spo1d_run(qd_c128* psi, const qd_c128* expV, const qd_c128* expVh,
                  const qd_c128* expK, int nx, int B, int nt, int nout,
                  qd_c128* snap, void* stream);
 
+/*
+ * Observables of B split-operator states psi [B][npts][ns] (npts = dims[0] ... dims[ndim-1]
+ * in C order, state index fastest: the layout of psi and snap of every qd_spo*_run), reduced
+ * on the device (replaces the host loops of SPO2.population / rdm_el, wpd.py:627-689, and
+ * ResultSPO2.get_population / position, wpd.py:104-160).  With chi(p) = M(p) psi(p),
+ * chi_a = sum_b basis[p][a][b] psi_b (wpd.py:651 einsum('ijab, ijb -> ija', d2a, psi);
+ * basis NULL: chi = psi):
+ *   rdm[B][ns][ns]   = weight * sum_p conj(chi_a(p)) chi_b(p)   (Hermitian by construction:
+ *                      the upper triangle is summed, the lower written as its conjugate, the
+ *                      diagonal -- the populations -- with imaginary part exactly 0)
+ *   mom[B][ndim][ns] = weight * sum_p x_d(p) |chi_a(p)|^2       (NULL: not computed)
+ * x0, x1, x2 are the coordinate axes [dims[d]] (read only when mom is given, where the axis of
+ * every used dimension must be non-NULL; the others may be NULL); weight is the volume element
+ * dx dy (dz).  1 <= ndim <= 3, npts < 2^31, 1 <= ns <= 1024, 1 <= B <= 65535.  ns <= 4 reads
+ * each state once with the accumulators in registers; larger ns makes one pass per (a <= b)
+ * pair.  The summation order depends on the shape alone (no atomics): the result is
+ * bit-identical from call to call and under graph replay.
+ */
+int qd_spo_observe(const qd_c128* psi, long B, const int* dims, int ndim, int ns,
+                   const qd_c128* basis, const double* x0, const double* x1,
+                   const double* x2, double weight, qd_c128* rdm, double* mom,
+                   void* stream);
+
+/*
+ * qd_spo2_run_batch / qd_spo2_run_ex (Strang structure only: V/2 K V/2, the arithmetic of
+ * run(return_states=True); expKy != NULL: Jacobi KEO) with qd_spo_observe applied to the state
+ * after every nout steps inside the run: rdm [B][nsteps/nout][ns][ns] and mom
+ * [B][nsteps/nout][2][ns] (or NULL), with basis [nx][ny][ns][ns] (or NULL), axes x [nx],
+ * y [ny] and weight as in qd_spo_observe.  snap [B][nsteps/nout][nx][ny][ns] keeps the states
+ * too; snap = NULL keeps none: the recorded state then goes to one reused scratch slot (it
+ * exists only in the row pass's fused snapshot store), so the run needs one state of scratch
+ * instead of nsteps/nout.  psi, the snapshots and the kernels of the propagation are those of
+ * the plain entry points bit for bit: B = 1 (or expKy) takes qd_spo2_run_ex's shape dispatch
+ * member by member, B > 1 qd_spo2_run_batch's.
+ */
+int qd_spo2_run_observed(qd_c128* psi, int B, const qd_c128* expVh, const qd_c128* expK,
+                         const qd_c128* expKy, int nx, int ny, int ns, int nsteps, int nout,
+                         qd_c128* snap, const qd_c128* basis, const double* x,
+                         const double* y, double weight, qd_c128* rdm, double* mom,
+                         void* stream);
+
 /* ------------------------------------------------------------ DEOM / HEOM -- */
 /*
  * RK4 propagation of B independent DEOM hierarchies (dissipaton equation of
@@ -531,6 +572,21 @@ int qd_spo3_run(qd_c128* psi, const qd_c128* expVh, const qd_c128* expK, int nx,
 int qd_spo3_run_axes(qd_c128* psi, const qd_c128* expVh, const qd_c128* mx,
                      const qd_c128* my, const qd_c128* mz, int nx, int ny, int nz, int ns,
                      int nsteps, int nout, qd_c128* snap, void* stream);
+
+/*
+ * qd_spo3_run / qd_spo3_run_axes with qd_spo_observe applied to the state after every nout
+ * steps inside the run (as qd_spo2_run_observed).  Exactly one of expK [nx][ny][nz] and
+ * (mx, my, mz) is non-NULL and selects qd_spo3_run's or qd_spo3_run_axes' step, with that
+ * entry point's shape limits and dispatch.  rdm [nsteps/nout][ns][ns], mom
+ * [nsteps/nout][3][ns] (or NULL), basis [nx][ny][nz][ns][ns] (or NULL), axes x, y, z, weight
+ * = dx dy dz; snap [nsteps/nout][nx][ny][nz][ns], or NULL to keep no states (one scratch slot).
+ */
+int qd_spo3_run_observed(qd_c128* psi, const qd_c128* expVh, const qd_c128* expK,
+                         const qd_c128* mx, const qd_c128* my, const qd_c128* mz, int nx,
+                         int ny, int nz, int ns, int nsteps, int nout, qd_c128* snap,
+                         const qd_c128* basis, const double* x, const double* y,
+                         const double* z, double weight, qd_c128* rdm, double* mom,
+                         void* stream);
 
 /*
  * RK4 with a dense Liouville-space generator, d v/dt = L v (B vectors).

@@ -151,4 +151,46 @@ int cgemm_splitk_slabs(const c128* A, const c128* B, int Mp, int Kp, int Np, c12
 // order, X[k1 + (L / *l2) k2] at slot *l2 k1 + k2; else natural order.  O L I < 2^31.
 int fft_lines(c128* x, long O, int L, long I, bool inv, hipStream_t st, int* l2);
 
+// Observables of SPO states psi [npts][ns] (spo_observe.hip, qd_spo_observe): the electronic reduced density matrix
+// rdm[a][b] = w sum_p conj(chi_a) chi_b and the first moments mom[d][a] = w sum_p x_d(p) |chi_a|^2 of chi = M psi.
+// prepare() takes the call's scratch once (every workspace() call is a slab of its own); launch() queues the reduction
+// of B states at psi + m * psi_bstride into row `rec` of each member's output.  Summation order is a function of the
+// shape alone: no atomics, no counters, nothing to re-zero between launches or graph replays.
+struct SpoObserver {
+  int dims[3] = {1, 1, 1};
+  int ndim = 0, ns = 0, B = 1;
+  const c128* basis = nullptr;                       // [npts][ns][ns] or null (chi = psi)
+  const double* x[3] = {nullptr, nullptr, nullptr};  // axes (mom only)
+  double weight = 1.0;
+  c128* rdm = nullptr;                               // member m, row r at rdm + m * rdm_bstride + r * ns * ns
+  double* mom = nullptr;                             // member m, row r at mom + m * mom_bstride + r * ndim * ns; or null
+  size_t rdm_bstride = 0, mom_bstride = 0;
+  // scratch (prepare)
+  double* part = nullptr;
+  c128* chi = nullptr;
+  int G = 0, NV = 0;
+  long npts = 0;
+  int prepare(hipStream_t st);
+  int launch(const c128* psi, size_t psi_bstride, int rec, hipStream_t st) const;
+};
+
+// Where a run loop's fused snapshot store goes.  The true state after a recorded step exists only in that store
+// (IFFT -> V/2 -> [snapshot] -> V/2 -> FFT; psi in memory is mid-pipeline), so an observed run without snapshots
+// still takes them, into one reused slot: stream order makes the single slot safe, since the observer that reads it is
+// queued right behind the pass that wrote it and before the next one.  With no observer (the plain entry points) the
+// sink is the caller's snap pointer and nothing else: the loops launch exactly what they launched on a bare pointer.
+struct SnapSink {
+  c128* snap = nullptr;   // caller's snapshots [nrec][grid], or null
+  c128* slot = nullptr;   // one scratch state ([B][grid] in the batch loop) when snap is null and obs is set
+  size_t grid_elems = 0;
+  size_t bstride = 0;     // between the members of a batch at the address at() returns
+  const SpoObserver* obs = nullptr;
+  explicit operator bool() const { return snap || slot; }
+  c128* at(int rec) const { return snap ? snap + (size_t)rec * grid_elems : slot; }
+  int taken(int rec, hipStream_t st) const { return obs ? obs->launch(at(rec), bstride, rec, st) : QD_OK; }
+};
+// Argument checks of an observer's part of a call (before any HIP call); `who` names the entry point in the message.
+int spo_observer_check(const char* who, const int* dims, int ndim, int ns, long B, const double* const x[3],
+                       const void* rdm, const void* mom);
+
 }  // namespace qd

@@ -1175,8 +1175,8 @@ __global__ void axis_factor_kernel(const c128* m0, const c128* m1, const c128* m
 // with the point operators: the previous step's closing half, the snapshot, this step's opening half), y (mid axis),
 // x (columns) -- where the non-separable path needs four (the x pass multiplies the 3-D exp_K between the y and z
 // transforms, so both are undone in passes of their own).
-int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout, c128* snap,
-                   hipStream_t st) {
+int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout,
+                   const SnapSink& snap, hipStream_t st) {
   void* w = nullptr;
   int rc = workspace(WS_SPO, (size_t)4 * 64 * sizeof(c128), &w, st);
   if (rc) return rc;
@@ -1186,7 +1186,6 @@ int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, in
   hipLaunchKernelGGL(axis_factor_kernel, dim3(3), dim3(64), 0, st, m[0], m[1], m[2], 64, d);
   QD_HIP(hipGetLastError());
   const int rows = 64 * 64, nyz = 64 * 64, inner = 64 * ns;
-  const size_t grid_elems = (size_t)64 * 64 * 64 * ns;
   auto zpass = [&](int flags, c128* sp) -> int {
     if (ns == 1) hipLaunchKernelGGL(spo_row64_kernel<1>, dim3(rows / 16), dim3(256), 0, st, psi, Vh, tw, flags, sp, d + 128);
     else hipLaunchKernelGGL(spo_row64_kernel<2>, dim3(rows / 16), dim3(256), 0, st, psi, Vh, tw, flags, sp, d + 128);
@@ -1210,7 +1209,8 @@ int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, in
     const bool take = snap && s > 0 && s % nout == 0;
     int flags = (s > 0 ? ROW_VH1 : 0) | (take ? ROW_SNAP : 0);
     if (s < nsteps) flags |= ROW_VH2 | ROW_FWD | ROW_KZ;
-    if ((rc = zpass(flags, take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr))) return rc;
+    if ((rc = zpass(flags, take ? snap.at(s / nout - 1) : nullptr))) return rc;
+    if (take && (rc = snap.taken(s / nout - 1, st))) return rc;
     if (s == nsteps) break;
     if ((rc = ypass())) return rc;
     if ((rc = xpass())) return rc;
@@ -1220,7 +1220,7 @@ int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, in
 
 // spo_gen.hip: every grid the specialised power-of-two kernels below do not cover
 int spo_generic_run(c128* psi, const c128* expVh, const c128* expV, const c128* expK, const c128* expKy,
-                    const int* dims, int D, int ns, int nsteps, int nout, c128* snap, hipStream_t st);
+                    const int* dims, int D, int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st);
 int spo1d_generic_run(c128* psi, const c128* expV, const c128* expVh, const c128* expK, int nx, int B, int nt,
                       int nout, c128* snap, hipStream_t st);
 int spo_expm_run(const void* v, int v_complex, int herm, long npts, int ns, double dt, c128* expV, c128* expVh,
@@ -1230,9 +1230,11 @@ int spo_expm_run(const void* v, int v_complex, int herm, long npts, int ns, doub
 
 using namespace qd;
 
-extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expV_, const qd_c128* expK_,
-                              const qd_c128* expKy_, int nx, int ny, int ns, int nsteps, int nout, qd_c128* snap_,
-                              void* stream) {
+// qd_spo2_run_ex with its snapshot store behind a sink (qd_common.hpp): the plain entry points pass the caller's
+// pointer and no observer, qd_spo2_run_observed the observer and, without snapshots, its scratch slot.
+static int spo2_run_sink(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expV_, const qd_c128* expK_,
+                         const qd_c128* expKy_, int nx, int ny, int ns, int nsteps, int nout, const SnapSink& snap,
+                         void* stream) {
   WsScope wss_((hipStream_t)stream);  // call-scoped scratch (qd_runtime.hip)
   QD_CHECK_ARG(psi_ && expVh_ && expK_, "qd_spo2_run_ex: null pointer");
   QD_CHECK_ARG(nx >= 1 && ny >= 1 && ns >= 1, "qd_spo2_run_ex: nx=%d ny=%d ns=%d", nx, ny, ns);
@@ -1248,13 +1250,12 @@ extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c12
     if (!special) {
       const int dims[2] = {nx, ny};
       return spo_generic_run((c128*)psi_, (const c128*)expVh_, (const c128*)expV_, (const c128*)expK_,
-                             (const c128*)expKy_, dims, 2, ns, nsteps, nout, (c128*)snap_, (hipStream_t)stream);
+                             (const c128*)expKy_, dims, 2, ns, nsteps, nout, snap, (hipStream_t)stream);
     }
   }
   hipStream_t st = (hipStream_t)stream;
   c128* psi = (c128*)psi_;
   const c128* expVh = (const c128*)expVh_;
-  c128* snap = (c128*)snap_;
   void* w = nullptr;
   const size_t nkt = (size_t)nx * ny;
   int rc = workspace(WS_SPO, (nkt + nx + ny) * sizeof(c128), &w, st);
@@ -1306,12 +1307,11 @@ extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c12
     QD_HIP(hipGetLastError());
     return QD_OK;
   };
-  const size_t grid_elems = (size_t)nx * ny * ns;
   if ((rc = row(ROW_VH1 | ROW_FWD | ky, nullptr, expVh))) return rc;
   for (int s = 1; s <= nsteps; ++s) {
     if ((rc = col())) return rc;
     const bool take = snap && (s % nout == 0);
-    c128* sp = take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr;
+    c128* sp = take ? snap.at(s / nout - 1) : nullptr;
     int flags = ROW_INV | ROW_VH1 | (take ? ROW_SNAP : 0);
     if (expV) {  // merged: IFFT_y -> V -> [snapshot] -> FFT_y
       flags |= ROW_FWD | ky;
@@ -1319,6 +1319,7 @@ extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c12
       flags |= ROW_VH2 | ROW_FWD | ky;
     }
     if ((rc = row(flags, sp, expV ? expV : expVh))) return rc;
+    if (take && (rc = snap.taken(s / nout - 1, st))) return rc;
   }
   if (expV) {  // merged tail (wpd.py:752-755): K, then V/2
     if ((rc = col())) return rc;
@@ -1327,33 +1328,72 @@ extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c12
   return QD_OK;
 }
 
+static SnapSink plain_sink(qd_c128* snap, size_t grid_elems) {
+  SnapSink k;
+  k.snap = (c128*)snap;
+  k.grid_elems = grid_elems;
+  return k;
+}
+
+extern "C" int qd_spo2_run_ex(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expV_, const qd_c128* expK_,
+                              const qd_c128* expKy_, int nx, int ny, int ns, int nsteps, int nout, qd_c128* snap_,
+                              void* stream) {
+  return spo2_run_sink(psi_, expVh_, expV_, expK_, expKy_, nx, ny, ns, nsteps, nout,
+                       plain_sink(snap_, (size_t)nx * ny * ns), stream);
+}
+
 extern "C" int qd_spo2_run(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny, int ns,
                            int nsteps, int nout, qd_c128* snap_, void* stream) {
   return qd_spo2_run_ex(psi_, expVh_, nullptr, expK_, nullptr, nx, ny, ns, nsteps, nout, snap_, stream);
 }
 
-extern "C" int qd_spo2_run_batch(qd_c128* psi_, int B, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny,
-                                 int ns, int nsteps, int nout, qd_c128* snap_, void* stream) {
+// qd_spo2_run_batch behind a sink; obs (or null) carries the outputs of all B members, and the members that run one
+// at a time observe through a copy of it that points at their own rows.
+static int spo2_batch_sink(qd_c128* psi_, int B, const qd_c128* expVh_, const qd_c128* expK_, const qd_c128* expKy_,
+                           int nx, int ny, int ns, int nsteps, int nout, qd_c128* snap_, SpoObserver* obs,
+                           void* stream) {
   WsScope wss_((hipStream_t)stream);  // call-scoped scratch (qd_runtime.hip)
   QD_CHECK_ARG(psi_ && expVh_ && expK_, "qd_spo2_run_batch: null pointer");
   QD_CHECK_ARG(B >= 1 && B <= 65535, "qd_spo2_run_batch: B=%d outside [1, 65535]", B);
   QD_CHECK_ARG(nsteps >= 0 && nout >= 1, "qd_spo2_run_batch: nsteps=%d nout=%d", nsteps, nout);
   const size_t grid_elems = (size_t)nx * ny * ns;
   const int nsave = nsteps / nout;
-  if (!(nx == 256 && ny == 256 && ns <= 2)) {
+  hipStream_t st = (hipStream_t)stream;
+  SnapSink snap = plain_sink(snap_, grid_elems);
+  // the 256 x 256 batch loop; an observed single wavefunction keeps qd_spo2_run_ex's dispatch, as SPO2.run does
+  const bool batched = nx == 256 && ny == 256 && ns <= 2 && !expKy_ && (!obs || B > 1);
+  if (obs && nsave) {
+    if (!snap_) {   // one reused state: per member in the batch loop, for all of them in turn otherwise
+      void* slot = nullptr;
+      QD_TRY(workspace(WS_SPO, (size_t)(batched ? B : 1) * grid_elems * sizeof(c128), &slot, st));
+      snap.slot = (c128*)slot;
+    }
+    snap.bstride = snap_ ? (size_t)nsave * grid_elems : grid_elems;
+    QD_TRY(obs->prepare(st));
+    snap.obs = obs;
+  }
+  if (!batched) {
     // other shapes: one member at a time on the single-wavefunction path
+    SpoObserver one;
+    if (snap.obs) {
+      one = *obs;
+      one.B = 1;
+    }
     for (int w = 0; w < B; ++w) {
-      const int rc = qd_spo2_run_ex(psi_ + w * grid_elems, expVh_, nullptr, expK_, nullptr, nx, ny, ns, nsteps, nout,
-                                    snap_ ? snap_ + (size_t)w * nsave * grid_elems : nullptr, stream);
-      if (rc) return rc;
+      SnapSink k = plain_sink(snap_ ? snap_ + (size_t)w * nsave * grid_elems : nullptr, grid_elems);
+      if (snap.obs) {
+        one.rdm = obs->rdm + (size_t)w * obs->rdm_bstride;
+        one.mom = obs->mom ? obs->mom + (size_t)w * obs->mom_bstride : nullptr;
+        k.slot = snap.slot;   // member w's snapshots are observed before member w + 1 starts
+        k.obs = &one;
+      }
+      QD_TRY(spo2_run_sink(psi_ + w * grid_elems, expVh_, nullptr, expK_, expKy_, nx, ny, ns, nsteps, nout, k, stream));
     }
     return QD_OK;
   }
   if (nsteps == 0) return QD_OK;
-  hipStream_t st = (hipStream_t)stream;
   c128* psi = (c128*)psi_;
   const c128* U = (const c128*)expVh_;
-  c128* snap = (c128*)snap_;
   void* w = nullptr;
   const size_t nkt = (size_t)nx * ny;
   int rc = workspace(WS_SPO, (nkt + nx + ny) * sizeof(c128), &w, st);
@@ -1366,7 +1406,7 @@ extern "C" int qd_spo2_run_batch(qd_c128* psi_, int B, const qd_c128* expVh_, co
   hipLaunchKernelGGL(transpose_scale_kernel, dim3((int)std::min<size_t>((nkt + 255) / 256, 4096)), dim3(256), 0, st,
                      (const c128*)expK_, nx, ny, 1.0 / ((double)nx * ny), expKT);
   QD_HIP(hipGetLastError());
-  const size_t sstride = (size_t)nsave * grid_elems;
+  const size_t sstride = snap.slot ? grid_elems : (size_t)nsave * grid_elems;
   // ns = 2: a wave per member, 4 members per workgroup sharing the staged point operators (64 wavepackets: 476k
   // wavepacket-steps/s against 428k for 2-member groups of the single-row kernel); the column pass in tiles of 8
   // columns (503k against 477k for 4)
@@ -1394,11 +1434,45 @@ extern "C" int qd_spo2_run_batch(qd_c128* psi_, int B, const qd_c128* expVh_, co
     col();
     QD_HIP(hipGetLastError());
     const bool take = snap && (s % nout == 0);
-    c128* sp = take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr;
+    c128* sp = take ? snap.at(s / nout - 1) : nullptr;
     row(ROW_INV | ROW_VH1 | (take ? ROW_SNAP : 0) | (s < nsteps ? ROW_VH2 | ROW_FWD : 0), sp);
     QD_HIP(hipGetLastError());
+    if (take) QD_TRY(snap.taken(s / nout - 1, st));
   }
   return QD_OK;
+}
+
+extern "C" int qd_spo2_run_batch(qd_c128* psi_, int B, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny,
+                                 int ns, int nsteps, int nout, qd_c128* snap_, void* stream) {
+  return spo2_batch_sink(psi_, B, expVh_, expK_, nullptr, nx, ny, ns, nsteps, nout, snap_, nullptr, stream);
+}
+
+extern "C" int qd_spo2_run_observed(qd_c128* psi, int B, const qd_c128* expVh, const qd_c128* expK,
+                                    const qd_c128* expKy, int nx, int ny, int ns, int nsteps, int nout, qd_c128* snap,
+                                    const qd_c128* basis, const double* x, const double* y, double weight,
+                                    qd_c128* rdm, double* mom, void* stream) {
+  QD_CHECK_ARG(psi && expVh && expK, "qd_spo2_run_observed: null pointer");
+  QD_CHECK_ARG(nx >= 1 && ny >= 1, "qd_spo2_run_observed: nx=%d ny=%d", nx, ny);
+  const int dims[2] = {nx, ny};
+  const double* const ax[3] = {x, y, nullptr};
+  QD_TRY(spo_observer_check("qd_spo2_run_observed", dims, 2, ns, B, ax, rdm, mom));
+  QD_CHECK_ARG(nsteps >= 0 && nout >= 1, "qd_spo2_run_observed: nsteps=%d nout=%d", nsteps, nout);
+  const size_t nrec = (size_t)(nsteps / nout);
+  SpoObserver o;
+  o.ndim = 2;
+  o.dims[0] = nx;
+  o.dims[1] = ny;
+  o.x[0] = x;
+  o.x[1] = y;
+  o.ns = ns;
+  o.B = B;
+  o.basis = (const c128*)basis;
+  o.weight = weight;
+  o.rdm = (c128*)rdm;
+  o.mom = mom;
+  o.rdm_bstride = nrec * ns * ns;
+  o.mom_bstride = nrec * 2 * ns;
+  return spo2_batch_sink(psi, B, expVh, expK, expKy, nx, ny, ns, nsteps, nout, snap, &o, stream);
 }
 
 extern "C" int qd_spo1d_run(qd_c128* psi_, const qd_c128* expV_, const qd_c128* expVh_, const qd_c128* expK_, int nx,
@@ -1426,8 +1500,8 @@ extern "C" int qd_spo1d_run(qd_c128* psi_, const qd_c128* expV_, const qd_c128* 
   return QD_OK;
 }
 
-extern "C" int qd_spo3_run(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny, int nz, int ns,
-                           int nsteps, int nout, qd_c128* snap_, void* stream) {
+static int spo3_run_sink(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny, int nz, int ns,
+                         int nsteps, int nout, const SnapSink& snap, void* stream) {
   WsScope wss_((hipStream_t)stream);  // call-scoped scratch (qd_runtime.hip)
   QD_CHECK_ARG(psi_ && expVh_ && expK_, "qd_spo3_run: null pointer");
   QD_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && ns >= 1, "qd_spo3_run: nx=%d ny=%d nz=%d ns=%d", nx, ny, nz, ns);
@@ -1442,13 +1516,12 @@ extern "C" int qd_spo3_run(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* 
     if (!special) {
       const int dims[3] = {nx, ny, nz};
       return spo_generic_run((c128*)psi_, (const c128*)expVh_, nullptr, (const c128*)expK_, nullptr, dims, 3, ns,
-                             nsteps, nout, (c128*)snap_, (hipStream_t)stream);
+                             nsteps, nout, snap, (hipStream_t)stream);
     }
   }
   hipStream_t st = (hipStream_t)stream;
   c128* psi = (c128*)psi_;
   const c128* expVh = (const c128*)expVh_;
-  c128* snap = (c128*)snap_;
   const int nyz = ny * nz;
   const size_t nk = (size_t)nx * nyz;
   void* w = nullptr;
@@ -1595,20 +1668,75 @@ extern "C" int qd_spo3_run(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* 
     QD_HIP(hipGetLastError());
     return QD_OK;
   };
-  const size_t grid_elems = nk * ns;
   if ((rc = row(ROW_VH1 | ROW_FWD, nullptr))) return rc;
   if ((rc = mid(false))) return rc;
   for (int s = 1; s <= nsteps; ++s) {
     if ((rc = col())) return rc;
     if ((rc = mid(true))) return rc;
     const bool take = snap && (s % nout == 0);
-    c128* sp = take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr;
+    c128* sp = take ? snap.at(s / nout - 1) : nullptr;
     int flags = ROW_INV | ROW_VH1 | (take ? ROW_SNAP : 0);
     if (s < nsteps) flags |= ROW_VH2 | ROW_FWD;
     if ((rc = row(flags, sp))) return rc;
+    if (take && (rc = snap.taken(s / nout - 1, st))) return rc;
     if (s < nsteps && (rc = mid(false))) return rc;
   }
   return QD_OK;
+}
+
+extern "C" int qd_spo3_run(qd_c128* psi_, const qd_c128* expVh_, const qd_c128* expK_, int nx, int ny, int nz, int ns,
+                           int nsteps, int nout, qd_c128* snap_, void* stream) {
+  return spo3_run_sink(psi_, expVh_, expK_, nx, ny, nz, ns, nsteps, nout,
+                       plain_sink(snap_, (size_t)nx * ny * nz * ns), stream);
+}
+
+namespace qd {
+// spo_dense.hip: qd_spo3_run_axes behind a sink
+int spo3_axes_sink(c128* psi, const c128* expVh, const c128* mx, const c128* my, const c128* mz, int nx, int ny, int nz,
+                   int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st);
+}  // namespace qd
+
+extern "C" int qd_spo3_run_observed(qd_c128* psi, const qd_c128* expVh, const qd_c128* expK, const qd_c128* mx,
+                                    const qd_c128* my, const qd_c128* mz, int nx, int ny, int nz, int ns, int nsteps,
+                                    int nout, qd_c128* snap, const qd_c128* basis, const double* x, const double* y,
+                                    const double* z, double weight, qd_c128* rdm, double* mom, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip): the observer's partial rows and the snapshot slot
+  QD_CHECK_ARG(psi && expVh, "qd_spo3_run_observed: null pointer");
+  const bool axes = mx && my && mz;
+  QD_CHECK_ARG((expK != nullptr) != (mx || my || mz) && (expK || axes),
+               "qd_spo3_run_observed: exactly one of expK and (mx, my, mz) selects the kinetic step");
+  QD_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1, "qd_spo3_run_observed: nx=%d ny=%d nz=%d", nx, ny, nz);
+  const int dims[3] = {nx, ny, nz};
+  const double* const ax[3] = {x, y, z};
+  QD_TRY(spo_observer_check("qd_spo3_run_observed", dims, 3, ns, 1, ax, rdm, mom));
+  QD_CHECK_ARG(nsteps >= 0 && nout >= 1, "qd_spo3_run_observed: nsteps=%d nout=%d", nsteps, nout);
+  const size_t grid_elems = (size_t)nx * ny * nz * ns;
+  SpoObserver o;
+  o.ndim = 3;
+  for (int d = 0; d < 3; ++d) {
+    o.dims[d] = dims[d];
+    o.x[d] = ax[d];
+  }
+  o.ns = ns;
+  o.basis = (const c128*)basis;
+  o.weight = weight;
+  o.rdm = (c128*)rdm;
+  o.mom = mom;
+  SnapSink k = plain_sink(snap, grid_elems);
+  if (nsteps / nout) {
+    if (!snap) {
+      void* slot = nullptr;
+      QD_TRY(workspace(WS_SPO, grid_elems * sizeof(c128), &slot, st));
+      k.slot = (c128*)slot;
+    }
+    QD_TRY(o.prepare(st));
+    k.obs = &o;
+  }
+  if (axes)
+    return spo3_axes_sink((c128*)psi, (const c128*)expVh, (const c128*)mx, (const c128*)my, (const c128*)mz, nx, ny,
+                          nz, ns, nsteps, nout, k, st);
+  return spo3_run_sink(psi, expVh, expK, nx, ny, nz, ns, nsteps, nout, k, stream);
 }
 
 extern "C" int qd_spo_expv(const void* v, int v_complex, long npts, int ns, double dt, qd_c128* expV_,

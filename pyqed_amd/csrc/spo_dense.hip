@@ -132,8 +132,8 @@ __global__ void spo_half_kernel(c128* psi, const c128* Vh, size_t npts) {
 }
 
 template <int NS>
-int run_axes(c128* psi, const c128* Vh, const c128* const m[3], const int d[3], int nsteps, int nout, c128* snap,
-             hipStream_t st) {
+int run_axes(c128* psi, const c128* Vh, const c128* const m[3], const int d[3], int nsteps, int nout,
+             const SnapSink& snap, hipStream_t st) {
   const size_t npts = (size_t)d[0] * d[1] * d[2];
   const int hb = (int)std::min<size_t>((npts + 255) / 256, 4096);
   hipLaunchKernelGGL(spo_half_kernel<NS>, dim3(hb), dim3(256), 0, st, psi, Vh, npts);
@@ -153,9 +153,10 @@ int run_axes(c128* psi, const c128* Vh, const c128* const m[3], const int d[3], 
         hipLaunchKernelGGL(spo_axis_kernel<0>, grid, block, 0, st, p);
       } else {
         p.Vh = Vh;
-        p.snap = (snap && (s + 1) % nout == 0) ? snap + (size_t)((s + 1) / nout - 1) * npts * NS : nullptr;
+        p.snap = (snap && (s + 1) % nout == 0) ? snap.at((s + 1) / nout - 1) : nullptr;
         p.vh2 = s + 1 < nsteps;
         hipLaunchKernelGGL(spo_axis_kernel<NS>, grid, block, 0, st, p);
+        if (p.snap) QD_TRY(snap.taken((s + 1) / nout - 1, st));
       }
       QD_HIP(hipGetLastError());
     }
@@ -166,15 +167,12 @@ int run_axes(c128* psi, const c128* Vh, const c128* const m[3], const int d[3], 
 }  // namespace
 
 // spo.hip: 64^3 grids on the register transforms (three separable passes per step)
-int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout, c128* snap,
-                   hipStream_t st);
-}  // namespace qd
+int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout,
+                   const SnapSink& snap, hipStream_t st);
 
-using namespace qd;
-
-extern "C" int qd_spo3_run_axes(qd_c128* psi, const qd_c128* expVh, const qd_c128* mx, const qd_c128* my,
-                                const qd_c128* mz, int nx, int ny, int nz, int ns, int nsteps, int nout, qd_c128* snap,
-                                void* stream) {
+// qd_spo3_run_axes with its snapshot store behind a sink (qd_common.hpp)
+int spo3_axes_sink(c128* psi, const c128* expVh, const c128* mx, const c128* my, const c128* mz, int nx, int ny, int nz,
+                   int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st) {
   QD_CHECK_ARG(psi && expVh && mx && my && mz, "qd_spo3_run_axes: null pointer");
   QD_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && nx <= SD_MAXN && ny <= SD_MAXN && nz <= SD_MAXN,
                "qd_spo3_run_axes: nx=%d ny=%d nz=%d outside [1, %d]", nx, ny, nz, SD_MAXN);
@@ -183,13 +181,26 @@ extern "C" int qd_spo3_run_axes(qd_c128* psi, const qd_c128* expVh, const qd_c12
   if (nsteps == 0) return QD_OK;
   const c128* m[3] = {(const c128*)mx, (const c128*)my, (const c128*)mz};
   const int d[3] = {nx, ny, nz};
-  hipStream_t st = (hipStream_t)stream;
   if (nx == 64 && ny == 64 && nz == 64) {
     WsScope wss_(st);
     note_path("spo3_sep64");
-    return spo3_sep64_run((c128*)psi, (const c128*)expVh, m, ns, nsteps, nout, (c128*)snap, st);
+    return spo3_sep64_run(psi, expVh, m, ns, nsteps, nout, snap, st);
   }
   note_path("spo3_axes");
-  return ns == 1 ? run_axes<1>((c128*)psi, (const c128*)expVh, m, d, nsteps, nout, (c128*)snap, st)
-                 : run_axes<2>((c128*)psi, (const c128*)expVh, m, d, nsteps, nout, (c128*)snap, st);
+  return ns == 1 ? run_axes<1>(psi, expVh, m, d, nsteps, nout, snap, st)
+                 : run_axes<2>(psi, expVh, m, d, nsteps, nout, snap, st);
+}
+
+}  // namespace qd
+
+using namespace qd;
+
+extern "C" int qd_spo3_run_axes(qd_c128* psi, const qd_c128* expVh, const qd_c128* mx, const qd_c128* my,
+                                const qd_c128* mz, int nx, int ny, int nz, int ns, int nsteps, int nout, qd_c128* snap,
+                                void* stream) {
+  SnapSink k;
+  k.snap = (c128*)snap;
+  k.grid_elems = (size_t)nx * ny * nz * ns;
+  return spo3_axes_sink((c128*)psi, (const c128*)expVh, (const c128*)mx, (const c128*)my, (const c128*)mz, nx, ny, nz,
+                        ns, nsteps, nout, k, (hipStream_t)stream);
 }

@@ -958,21 +958,21 @@ struct Exec {
 };
 
 // Strang / merged step sequence of qd_spo2_run_ex / qd_spo3_run on a D-dimensional grid (D = 2, 3).
-int run_nd(Exec& x, const c128* Uh, const c128* Ufull, int nsteps, int nout, c128* snap, bool ky) {
+int run_nd(Exec& x, const c128* Uh, const c128* Ufull, int nsteps, int nout, const SnapSink& snap, bool ky) {
   const int D = x.D, last = D - 1;
   const int kyf = ky ? F_KY : 0;
-  const size_t grid_elems = (size_t)x.npts * x.ns;
   int rc;
   if (x.xpose) {   // D == 2, nsteps >= 1: the same pass sequence with the row pass storing into the other layout
     if ((rc = x.row_pass(F_PT1 | F_FWD | kyf, Uh, nullptr, nullptr, true))) return rc;
     for (int s = 1; s <= nsteps; ++s) {
       if ((rc = x.kin_pass())) return rc;
       const bool take = snap && (s % nout == 0);
-      c128* sp = take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr;
+      c128* sp = take ? snap.at(s / nout - 1) : nullptr;
       int flags = F_INV | F_PT1 | (take ? F_SNAP : 0);
       if (Ufull) flags |= F_FWD | kyf;
       else if (s < nsteps) flags |= F_PT2 | F_FWD | kyf;
       if ((rc = x.row_pass(flags, Ufull ? Ufull : Uh, Uh, sp, (flags & F_FWD) != 0))) return rc;
+      if (take && (rc = snap.taken(s / nout - 1, x.st))) return rc;
     }
     if (Ufull) {
       if ((rc = x.kin_pass())) return rc;
@@ -988,11 +988,12 @@ int run_nd(Exec& x, const c128* Uh, const c128* Ufull, int nsteps, int nout, c12
     for (int d = 1; d < last; ++d)
       if ((rc = x.pass(d, F_INV, nullptr, nullptr, nullptr))) return rc;
     const bool take = snap && (s % nout == 0);
-    c128* sp = take ? snap + (size_t)(s / nout - 1) * grid_elems : nullptr;
+    c128* sp = take ? snap.at(s / nout - 1) : nullptr;
     int flags = F_INV | F_PT1 | (take ? F_SNAP : 0);
     if (Ufull) flags |= F_FWD | kyf;
     else if (s < nsteps) flags |= F_PT2 | F_FWD | kyf;
     if ((rc = x.pass(last, flags, Ufull ? Ufull : Uh, Uh, sp))) return rc;
+    if (take && (rc = snap.taken(s / nout - 1, x.st))) return rc;
     if (flags & F_FWD)
       for (int d = last - 1; d >= 1; --d)
         if ((rc = x.pass(d, F_FWD, nullptr, nullptr, nullptr))) return rc;
@@ -1073,7 +1074,7 @@ int fft_lines(c128* x, long O, int L, long I, bool inv, hipStream_t st, int* l2)
 // Generic SPO2 / SPO3 run (any grid, any ns).  dims = {nx, ny} or {nx, ny, nz}; expK [dims] unscaled;
 // expKy [nx][ny] (2D Jacobi) or null; expV (merged V structure) or null.
 int spo_generic_run(c128* psi, const c128* expVh, const c128* expV, const c128* expK, const c128* expKy,
-                    const int* dims, int D, int ns, int nsteps, int nout, c128* snap, hipStream_t st) {
+                    const int* dims, int D, int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st) {
   using namespace spog;
   WsScope wss_(st);
   Exec x;

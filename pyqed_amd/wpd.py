@@ -4,6 +4,8 @@ Setup: grids and exp_K on the host like the reference's build (wpd.py:217-223, 4
 the per-point propagators exp(-i V dt), exp(-i V dt/2) on the device (qd_spo_expv: closed form for
 ns <= 2, a matrix exponential up to ns = 256).
 Every propagation step runs in libqdyn (qd_spo1d_run / qd_spo2_run_ex / qd_spo3_run).
+Populations, mean positions and the electronic reduced density matrix are reduced on the device
+(qd_spo_observe), after the run from states or inside it (run(..., observe=...), qd_spo*_run_observed).
 """
 from __future__ import annotations
 
@@ -44,9 +46,24 @@ class ResultSPO2(Result):
         self.y = None
         self.population = None
         self.xAve = None
+        self.rdm = None
+        self._recorded = None   # run(observe=...): (population, xAve, yAve) reduced on the device during the run
         self.nstates = self.psi0.shape[-1]
 
+    def _recorded_only(self):
+        """The observables a run(observe=...) recorded, when the run kept no states to recompute them from."""
+        rec = getattr(self, "_recorded", None)
+        return rec if rec is not None and len(self.psilist) <= 1 else None
+
     def get_population(self, fname=None, plot=False):
+        """wpd.py:104-127.  After run(observe=..., return_states=False) psilist holds only psi0 and the populations
+        recorded during the run are returned instead (extension)."""
+        rec = self._recorded_only()
+        if rec is not None:
+            p = self.population = rec[0]
+            if fname is not None:
+                np.savez(fname, p)
+            return p
         dx = interval(self.x)
         dy = interval(self.y)
         p = np.zeros((len(self.psilist), self.nstates))
@@ -58,6 +75,14 @@ class ResultSPO2(Result):
         return p
 
     def position(self, plot=False, fname=None):
+        """wpd.py:138-159.  After run(observe=..., return_states=False) the recorded mean positions are returned
+        (extension); xAve.npz is written either way."""
+        rec = self._recorded_only()
+        if rec is not None:
+            xAve, yAve = rec[1], rec[2]
+            self.xAve = [xAve, yAve]
+            np.savez('xAve', xAve, yAve)
+            return xAve, yAve
         x, y = self.x, self.y
         dx, dy = interval(x), interval(y)
         xAve = [np.einsum('ijn, i, ijn', psi.conj(), x, psi) * dx * dy for psi in self.psilist]
@@ -71,6 +96,66 @@ class ResultSPO2(Result):
 
 def _dev_c128(a, dev):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=complex))).to(dev)
+
+
+def _dev_f64(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=float))).to(dev)
+
+
+def _volume(axes):
+    return float(np.prod([interval(np.asarray(a)) for a in axes]))
+
+
+def observe_states(psi, axes, basis=None, weight=None, moments=True):
+    """Electronic reduced density matrix and first moments of split-operator states, reduced on the device
+    (qd_spo_observe; extension).
+
+    psi: [n0(, n1(, n2)), ns] or a batch [B, n0, ..., ns], a device tensor (used in place, not copied, when it is
+    contiguous complex128) or anything numpy reads; axes: the ndim = 1..3 coordinate arrays; basis: None or
+    M [n0, ..., ns, ns], applied as chi_a = sum_b M[p][a][b] psi_b; weight: the volume element (default: the product of
+    the axes' spacings).  Returns device tensors (rdm [(B,) ns, ns] complex, mom [(B,) ndim, ns] float or None):
+        rdm[a][b] = weight sum_p conj(chi_a) chi_b,    mom[d][a] = weight sum_p x_d(p) |chi_a|^2.
+    """
+    ndim = len(axes)
+    if isinstance(psi, torch.Tensor):
+        dev = psi.device
+        t = psi.to(dtype=torch.complex128).contiguous()
+    else:
+        dev = default_device()
+        t = _dev_c128(psi, dev)
+    _lib.ensure_device(dev)
+    if t.dim() not in (ndim + 1, ndim + 2):
+        raise ValueError(f"psi must be [{'n, ' * ndim}ns] or a batch of those; got {tuple(t.shape)}")
+    batched = t.dim() == ndim + 2
+    dims = tuple(t.shape[-1 - ndim:-1])
+    ns = int(t.shape[-1])
+    if dims != tuple(len(a) for a in axes):
+        raise ValueError(f"grid {dims} does not match the axes {tuple(len(a) for a in axes)}")
+    B = int(t.shape[0]) if batched else 1
+    if basis is not None:
+        basis = basis.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(basis, torch.Tensor) \
+            else _dev_c128(basis, dev)
+        if tuple(basis.shape) != dims + (ns, ns):
+            raise ValueError(f"basis must be {dims + (ns, ns)}; got {tuple(basis.shape)}")
+    if weight is None:
+        weight = _volume(axes)
+    ax = [_dev_f64(a, dev) for a in axes] if moments else []
+    rdm = torch.empty((B, ns, ns), dtype=torch.complex128, device=dev)
+    mom = torch.empty((B, ndim, ns), dtype=torch.float64, device=dev) if moments else None
+    cdims = (_lib.c_int * ndim)(*dims)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_spo_observe(t.data_ptr(), B, cdims, ndim, ns, _lib.ptr(basis),
+                                        *(ax[d].data_ptr() if moments and d < ndim else None for d in range(3)),
+                                        float(weight), rdm.data_ptr(), _lib.ptr(mom), _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_spo_observe")
+    if not batched:
+        return rdm[0], (mom[0] if moments else None)
+    return rdm, mom
+
+
+def _check_representation(representation):
+    if representation not in ('diabatic', 'adiabatic'):
+        raise ValueError('Representation = {}, which can only be diabatic or adiabatic'.format(representation))
 
 
 class SPO:
@@ -145,6 +230,7 @@ class _PointPropagators:
     _eV_dev = _eVh_dev = None
     _exp_V_host = _exp_V_half_host = None
     _d2a = _apes = None
+    _d2a_dev = None   # d2a on the device for observe='adiabatic' / population(..., 'adiabatic'): uploaded once per build
     _eig_pending = False
 
     @property
@@ -170,7 +256,7 @@ class _PointPropagators:
     def _host_eig(self):
         v = self._pot()
         w, u = np.linalg.eigh(v)          # ascending eigenvalues per point (phys.sort order)
-        self._d2a = u
+        self._d2a, self._d2a_dev = u, None
         self._apes = None if np.iscomplexobj(v) else w
         self._eig_pending = False
         return w, u
@@ -183,7 +269,7 @@ class _PointPropagators:
 
     @d2a.setter
     def d2a(self, u):
-        self._d2a = u
+        self._d2a, self._d2a_dev = u, None
 
     @property
     def apes(self):
@@ -217,8 +303,73 @@ class _PointPropagators:
         _lib.check(rc, "qd_spo_expv")
         self.exp_V, self.exp_V_half = None, None
         self._eV_dev, self._eVh_dev = eV, eVh
-        self._d2a = self._apes = None
+        self._d2a = self._apes = self._d2a_dev = None
         self._eig_pending = True
+
+    # ---- observables (qd_spo_observe); _axes() and nstates come from the solver class
+    def _obs_basis(self, observe, dev):
+        """The basis M of observe= / representation=: None ('diabatic'), d2a ('adiabatic') or an explicit
+        [..., ns, ns] array, on the device."""
+        if isinstance(observe, str):
+            _check_representation(observe)
+            if observe == 'diabatic':
+                return None
+            if self._d2a_dev is None or self._d2a_dev.device != dev:
+                u = self.d2a
+                if u is None:
+                    raise ValueError("the adiabatic representation needs d2a (build() first, or set it)")
+                self._d2a_dev = _dev_c128(u, dev)
+            return self._d2a_dev
+        shape = tuple(len(a) for a in self._axes()) + (self.nstates, self.nstates)
+        b = observe.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(observe, torch.Tensor) \
+            else _dev_c128(observe, dev)
+        if tuple(b.shape) != shape:
+            raise ValueError(f"observe basis must be {shape}; got {tuple(b.shape)}")
+        return b
+
+    def _states_dev(self, psi):
+        """(device tensor [B, grid..., ns], kind) of a state, a list of states, a stacked array or a device tensor;
+        kind is 'one', 'list' or 'batch'."""
+        nd = len(self._axes())
+        if isinstance(psi, list):
+            return _dev_c128(np.stack([np.asarray(p) for p in psi]) if psi else
+                             np.zeros((0,) + tuple(len(a) for a in self._axes()) + (self.nstates,)),
+                             default_device()), 'list'
+        t = psi if isinstance(psi, torch.Tensor) else _dev_c128(psi, default_device())
+        if t.dim() == nd + 1:
+            return t[None], 'one'
+        if t.dim() == nd + 2:
+            return t, 'batch'
+        raise ValueError(f"psi must be a state, a list of states or a stacked array; got shape {tuple(t.shape)}")
+
+    def _rdm_of(self, psi, basis_spec):
+        t, kind = self._states_dev(psi)
+        ns = self.nstates
+        if t.shape[0] == 0:
+            return np.zeros((0, ns, ns), complex), kind
+        basis = self._obs_basis(basis_spec, t.device)
+        rdm, _ = observe_states(t, self._axes(), basis=basis, moments=False)
+        return rdm.cpu().numpy(), kind
+
+    def _population(self, psi, representation):
+        _check_representation(representation)
+        rdm, kind = self._rdm_of(psi, representation)
+        P = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
+        return P[0] if kind == 'one' else P
+
+    def rdm_el(self, psi):
+        """Reduced electronic density matrix rho[a, b] = sum_p conj(psi_a) psi_b dV (wpd.py:760-794), reduced on the
+        device (qd_spo_observe): an ndarray (or device tensor) state gives [ns, ns], a list a list of [ns, ns]; a
+        stacked array [B, ..., ns] (extension) gives [B, ns, ns]."""
+        rdm, kind = self._rdm_of(psi, 'diabatic')
+        if kind == 'one':
+            return rdm[0]
+        return [rdm[k].copy() for k in range(len(rdm))] if kind == 'list' else rdm
+
+    def _first_row(self, psi0, basis, dev):
+        """rdm and mom of psi0: row 0 of a run's recorded observables."""
+        rdm, mom = observe_states(_dev_c128(psi0, dev), self._axes(), basis=basis)
+        return rdm[None], mom[None]
 
     def _point_ops_dev(self, dev, need_full=False):
         eVh = self._eVh_dev if self._eVh_dev is not None else _dev_c128(self.exp_V_half, dev)
@@ -292,6 +443,22 @@ class SPO2(_PointPropagators):
     def _pot(self):
         return self.v
 
+    def _axes(self):
+        return (self.x, self.y)
+
+    def population(self, psi, representation='diabatic', plot=False):
+        """Electronic populations (wpd.py:627-689), reduced on the device (qd_spo_observe): a list of states gives
+        [N, ns], an ndarray [nx, ny, ns] gives [ns]; a stacked array [B, nx, ny, ns] or a device tensor is also
+        accepted (extension; a device tensor is read in place, not copied).  The reference's ndarray branch dies on
+        np.close, which does not exist (wpd.py:648, 670); P is returned here.
+
+        representation='adiabatic' applies self.d2a exactly as the reference does, chi_a = sum_b d2a[i, j, a, b] psi_b
+        (wpd.py:664, 674): M = d2a, NOT its adjoint, so these are not projections on the eigenvector columns, and the
+        numbers depend on the eigenvector gauge: flipping the sign of one eigenvector column changes the result (by
+        1.5e-2 on a 32 x 32 two-state model).  For projections pass the adjoint explicitly,
+        run(..., observe=d2a.conj().swapaxes(-1, -2)).  Any other representation raises the reference's ValueError."""
+        return self._population(psi, representation)
+
     def build(self, dt, inertia=None):
         """wpd.py:496-625: the kinetic propagator (linear: exp_K on the 'ij' k-grid; jacobi:
         exp_Kx and exp_Ky[i, ky] = exp(-i ky^2 / (2 I(x_i)) dt) with I = masses[1]) and the per-point
@@ -345,11 +512,68 @@ class SPO2(_PointPropagators):
             states = [host[k] for k in range(nsnap)]
         return psi.cpu().numpy(), states
 
-    def run_batch(self, psi0s, dt=0.01, nt=1, nout=1, device=None):
+    def _kinetic_dev(self, dev):
+        if self.coords == 'jacobi':
+            return _dev_c128(np.broadcast_to(self.exp_Kx[:, None], (self.nx, self.ny)), dev), _dev_c128(self.exp_Ky, dev)
+        return _dev_c128(self.exp_K, dev), None
+
+    def _run_observed_dev(self, psi, dt, nt, nout, keep, basis, dev):
+        """qd_spo2_run_observed on the device batch psi [B, nx, ny, ns] (in place): Strang steps, observables after
+        every nout.  Returns (snap [B, nsnap, nx, ny, ns] or None, rdm [B, nsnap, ns, ns], mom [B, nsnap, 2, ns])."""
+        B, ns = int(psi.shape[0]), self.ns
+        nsnap = nt // nout
+        rows = max(nsnap, 1)
+        snap = torch.empty((B, nsnap, self.nx, self.ny, ns), dtype=torch.complex128, device=dev) \
+            if keep and nsnap else None
+        rdm = torch.zeros((B, rows, ns, ns), dtype=torch.complex128, device=dev)
+        mom = torch.zeros((B, rows, 2, ns), dtype=torch.float64, device=dev)
+        _, eVh = self._point_ops_dev(dev, need_full=False)
+        eK, eKy = self._kinetic_dev(dev)
+        x, y = _dev_f64(self.x, dev), _dev_f64(self.y, dev)
+        with torch.cuda.device(dev):
+            rc = _lib.load().qd_spo2_run_observed(psi.data_ptr(), B, eVh.data_ptr(), eK.data_ptr(), _lib.ptr(eKy),
+                                                  self.nx, self.ny, ns, int(nsnap * nout), int(nout), _lib.ptr(snap),
+                                                  _lib.ptr(basis), x.data_ptr(), y.data_ptr(),
+                                                  _volume((self.x, self.y)), rdm.data_ptr(), mom.data_ptr(),
+                                                  _lib.stream_ptr(dev))
+        _lib.check(rc, "qd_spo2_run_observed")
+        return snap, rdm[:, :nsnap], mom[:, :nsnap]
+
+    def _run_observed(self, psi0, dt, nt, t0, nout, return_states, observe):
+        """run(observe=...): Strang steps with the observables of psi0 and of the state after every nout steps."""
+        dev = default_device()
+        _lib.ensure_device(dev)
+        basis = self._obs_basis(observe, dev)
+        psi = _dev_c128(psi0, dev)[None].clone()
+        snap, rdm, mom = self._run_observed_dev(psi, dt, nt, nout, return_states, basis, dev)
+        rdm0, mom0 = self._first_row(psi0, basis, dev)
+        rdm = torch.cat([rdm0, rdm[0]]).cpu().numpy()
+        mom = torch.cat([mom0, mom[0]]).cpu().numpy()
+        r = ResultSPO2(dt=dt, psi0=psi0, Nt=nt, t0=t0, nout=nout)
+        r.x = self.x
+        r.y = self.y
+        r.psilist = [psi0]
+        if snap is not None:
+            host = snap[0].cpu().numpy()
+            r.psilist += [host[k] for k in range(host.shape[0])]
+        r.psi = psi[0].cpu().numpy()
+        r.rdm = rdm
+        r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
+        r.xAve = [mom[:, 0].sum(axis=-1), mom[:, 1].sum(axis=-1)]
+        r._recorded = (r.population, r.xAve[0], r.xAve[1])
+        return r
+
+    def run_batch(self, psi0s, dt=0.01, nt=1, nout=1, device=None, observe=None, keep_states=True):
         """Extension: B independent wavepackets psi0s [B, nx, ny, ns] on one potential, Strang steps as
         run(return_states=True) for each (qd_spo2_run_batch: one launch per pass for the whole batch).
         Returns (final states [B, nx, ny, ns], snapshots [B, nt//nout, nx, ny, ns]) as device tensors.
-        Jacobi coordinates run the _KEO_jacobi step structure (qd_spo2_run_ex) member by member."""
+        Jacobi coordinates run the _KEO_jacobi step structure (qd_spo2_run_ex) member by member.
+
+        observe ('diabatic', 'adiabatic' or a basis [nx, ny, ns, ns], see run) also reduces every recorded state
+        inside the run (qd_spo2_run_observed) and returns (psi, snap or None, obs): obs is a dict of device tensors,
+        rdm [B, nt//nout, ns, ns], mom [B, nt//nout, 2, ns] (mom[b, k, d, a] = <x_d> on state a) and population
+        [B, nt//nout, ns], for the recorded states only (no psi0 row).  keep_states=False keeps no snapshots: the
+        run then holds one scratch state per member instead of nt//nout."""
         self.build(dt=dt)
         dev = device or default_device()
         _lib.ensure_device(dev)
@@ -359,6 +583,9 @@ class SPO2(_PointPropagators):
         if tuple(psi.shape[1:]) != (self.nx, self.ny, self.ns):
             raise ValueError(f"psi0s must be [B, {self.nx}, {self.ny}, {self.ns}]")
         nsnap = nt // nout
+        if observe is not None:
+            snap, rdm, mom = self._run_observed_dev(psi, dt, nt, nout, keep_states, self._obs_basis(observe, dev), dev)
+            return psi, snap, {"rdm": rdm, "mom": mom, "population": torch.diagonal(rdm, dim1=-2, dim2=-1).real}
         snap = torch.empty((B, nsnap, self.nx, self.ny, self.ns), dtype=torch.complex128, device=dev) if nsnap \
             else None
         _, eVh = self._point_ops_dev(dev, need_full=False)
@@ -381,12 +608,22 @@ class SPO2(_PointPropagators):
         _lib.check(rc, "qd_spo2_run_batch")
         return psi, snap
 
-    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True):
+    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True, observe=None):
         """wpd.py:692-758.  return_states=True: psilist = [psi0] + the state after every nout
         Strang steps (nt//nout*nout steps).  return_states=False: the merged-V arithmetic runs
         but, as in the reference, psilist is only [psi0].  r.psi is the final state (the
-        reference leaves it unset)."""
+        reference leaves it unset).
+
+        observe (extension; None changes nothing): 'diabatic', 'adiabatic' (M = d2a, see population) or an explicit
+        basis [nx, ny, ns, ns].  The run then uses the Strang arithmetic whatever return_states says, and the
+        populations, reduced density matrix and mean positions of psi0 and of the state after every nout steps are
+        reduced on the device inside the run (qd_spo2_run_observed): r.population [nt//nout + 1, ns], r.rdm
+        [nt//nout + 1, ns, ns], r.xAve = [xAve, yAve] (summed over states, as position()).  return_states=True keeps
+        the states too; return_states=False keeps none -- psilist == [psi0], one state of device scratch instead of
+        nt//nout, Strang not merged arithmetic -- and get_population() / position() return the recorded arrays."""
         self.build(dt=dt)
+        if observe is not None:
+            return self._run_observed(psi0, dt, nt, t0, nout, return_states, observe)
         psi, states = self._propagate(psi0, dt, nt, nout, merged=not return_states)
         r = ResultSPO2(dt=dt, psi0=psi0, Nt=nt, t0=t0, nout=nout)
         r.x = self.x
@@ -471,10 +708,15 @@ class SPO2NH(SPO2):
         self.xAve = [xAve, yAve]
         return xAve, yAve
 
-    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True):
+    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True, observe=None):
         """wpd.py:1019-1077: Strang steps (return_states=True) or the merged structure
-        (False); psilist = [psi0] + the state after every nout steps in both cases; r.psi set."""
+        (False); psilist = [psi0] + the state after every nout steps in both cases; r.psi set.
+        observe: as SPO2.run (Strang steps; with return_states=False no states are kept, psilist == [psi0]); the
+        recorded quantities are the plain sums of SPO2.population / ResultSPO2.position, without the right-eigenvector
+        overlap of SPO2NH.position, and decay with the norm."""
         self.build(dt=dt)
+        if observe is not None:
+            return self._run_observed(psi0, dt, nt, t0, nout, return_states, observe)
         psi, states = self._propagate(psi0, dt, nt, nout, merged=not return_states)
         r = ResultSPO2(dt=dt, psi0=psi0, Nt=nt, t0=t0, nout=nout)
         r.x = self.x
@@ -576,9 +818,23 @@ class SPO3(_PointPropagators):
     def _pot(self):
         return self.V
 
-    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True):
+    def _axes(self):
+        return (self.x, self.y, self.z)
+
+    def population(self, psi, representation='diabatic'):
+        """Electronic populations of a state [nx, ny, nz, ns] -> [ns], a list -> [N, ns] (stacked arrays and device
+        tensors as SPO2.population), reduced on the device.  Deviation: the reference's SPO3.population (wpd.py:1316-1346)
+        indexes psi[:, :, j], which takes j along z, not the state, and weights by dx dy only; here the whole grid is
+        summed per state with dx dy dz.  representation as SPO2.population (extension)."""
+        return self._population(psi, representation)
+
+    def run(self, psi0, e_ops=[], dt=0.01, nt=1, t0=0., nout=1, return_states=True, observe=None):
         """wpd.py:1349-1411: nt//nout*nout Strang steps; psilist = state after every nout steps
-        (psi0 NOT included, as the reference); r.psi the final state."""
+        (psi0 NOT included, as the reference); r.psi the final state.
+
+        observe (extension, as SPO2.run): r.population [nt//nout + 1, ns], r.rdm [nt//nout + 1, ns, ns] and
+        r.xAve = [xAve, yAve, zAve] of psi0 (row 0) and of the state after every nout steps, reduced inside the run
+        (qd_spo3_run_observed); with return_states=False no states are kept (psilist == [])."""
         self.build(dt=dt)
         dev = default_device()
         _lib.ensure_device(dev)
@@ -586,9 +842,33 @@ class SPO3(_PointPropagators):
         nsnap = nt // nout
         psi = _dev_c128(psi0, dev)
         shape = (self.nx, self.ny, self.nz, self.nstates)
-        snap = torch.empty((nsnap,) + shape, dtype=torch.complex128, device=dev) if nsnap else None
+        observed = observe is not None
+        keep = return_states or not observed
+        snap = torch.empty((nsnap,) + shape, dtype=torch.complex128, device=dev) if nsnap and keep else None
         _, eVh = self._point_ops_dev(dev)
-        if self._use_axes():
+        if observed:
+            ns = self.nstates
+            basis = self._obs_basis(observe, dev)
+            rdm = torch.zeros((max(nsnap, 1), ns, ns), dtype=torch.complex128, device=dev)
+            mom = torch.zeros((max(nsnap, 1), 3, ns), dtype=torch.float64, device=dev)
+            if self._use_axes():
+                M = [_dev_c128(axis_propagator(k, m, dt), dev)
+                     for k, m in zip((self.kx, self.ky, self.kz), self.masses)]
+                kin = [None] + [m.data_ptr() for m in M]
+            else:
+                eK = _dev_c128(self.exp_K, dev)
+                kin = [eK.data_ptr(), None, None, None]
+            ax = [_dev_f64(a, dev) for a in self._axes()]
+            with torch.cuda.device(dev):
+                rc = _lib.load().qd_spo3_run_observed(psi.data_ptr(), eVh.data_ptr(), *kin, self.nx, self.ny, self.nz,
+                                                      ns, int(nsteps), int(nout), _lib.ptr(snap), _lib.ptr(basis),
+                                                      *(a.data_ptr() for a in ax), _volume(self._axes()),
+                                                      rdm.data_ptr(), mom.data_ptr(), _lib.stream_ptr(dev))
+            _lib.check(rc, "qd_spo3_run_observed")
+            rdm0, mom0 = self._first_row(psi0, basis, dev)
+            rdm = torch.cat([rdm0, rdm[:nsnap]]).cpu().numpy()
+            mom = torch.cat([mom0, mom[:nsnap]]).cpu().numpy()
+        elif self._use_axes():
             M = [_dev_c128(axis_propagator(k, m, dt), dev) for k, m in zip((self.kx, self.ky, self.kz), self.masses)]
             with torch.cuda.device(dev):
                 rc = _lib.load().qd_spo3_run_axes(psi.data_ptr(), eVh.data_ptr(), *(m.data_ptr() for m in M),
@@ -607,4 +887,8 @@ class SPO3(_PointPropagators):
             host = snap.cpu().numpy()
             r.psilist = [host[k] for k in range(nsnap)]
         r.psi = psi.cpu().numpy()
+        if observed:
+            r.rdm = rdm
+            r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
+            r.xAve = [mom[:, d].sum(axis=-1) for d in range(3)]
         return r
