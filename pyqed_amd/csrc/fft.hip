@@ -4,58 +4,19 @@
 //                 [outer][n][inner], fused with fftshift, a scale factor and the
 //                 phase exp(-/+ i freq x0) of pyqed.fft.fft / ifft (fft.py:11-102)
 //                 and fft2 (fft.py:104-126).  Any n (numpy.fft takes every length):
-//                 powers of two in [16, 1024] run one Stockham LDS kernel with the
+//                 powers of two in [16, 1024] run one Stockham LDS kernel (spo_fft_pow2.hpp) with the
 //                 epilogue fused; every other n runs the any-size engine of the SPO
 //                 grids (spo_gen.hip fft_lines: mixed radix 2/3/4/5/p <= 61 in LDS,
 //                 Bluestein, four-step for long smooth lengths, direct DFT for the
 //                 rest) on a copy, then one shift / scale / phase pass back.
 //   qd_dft2     : DFT at arbitrary momenta (fft.py:128-160 dft / dft2).
-#include "qd_common.hpp"
+#include "spo_fft_pow2.hpp"
+#include "spo_plan.hpp"
 
 #include <cstdlib>
 
 namespace qd {
 namespace {
-
-template <int L, bool INV>
-__device__ __forceinline__ c128* stockham(c128* a, c128* b, const c128* tw, int t) {
-#pragma unroll
-  for (int Ns = 1; Ns * 4 <= L; Ns *= 4) {
-    if (t < L / 4) {
-      const int j = t, k = j % Ns, base = k * (L / (4 * Ns));
-      c128 w1 = tw[base], w2 = tw[2 * base], w3 = tw[3 * base];
-      if (INV) { w1 = cconj(w1); w2 = cconj(w2); w3 = cconj(w3); }
-      const c128 v0 = a[j], v1 = cmul(a[j + L / 4], w1), v2 = cmul(a[j + L / 2], w2), v3 = cmul(a[j + 3 * L / 4], w3);
-      const c128 a0 = cadd(v0, v2), a1 = csub(v0, v2), b0 = cadd(v1, v3), b1 = csub(v1, v3);
-      const c128 ib1 = INV ? cmuli(b1) : cmulmi(b1);
-      const int d = (j / Ns) * Ns * 4 + k;
-      b[d] = cadd(a0, b0);
-      b[d + Ns] = cadd(a1, ib1);
-      b[d + 2 * Ns] = csub(a0, b0);
-      b[d + 3 * Ns] = csub(a1, ib1);
-    }
-    __syncthreads();
-    c128* tmp = a; a = b; b = tmp;
-  }
-  constexpr int lg = __builtin_ctz(L);
-  if (lg & 1) {
-    if (t < L / 4) {
-      constexpr int Ns = L / 2;
-      for (int h = 0; h < 2; ++h) {
-        const int j = t + h * (L / 4), k = j % Ns;
-        c128 w = tw[k];
-        if (INV) w = cconj(w);
-        const c128 v0 = a[j], v1 = cmul(a[j + L / 2], w);
-        const int d = (j / Ns) * Ns * 2 + k;
-        b[d] = cadd(v0, v1);
-        b[d + Ns] = csub(v0, v1);
-      }
-    }
-    __syncthreads();
-    c128* tmp = a; a = b; b = tmp;
-  }
-  return a;
-}
 
 // post-processing of one transformed row X (natural order) into data
 __device__ __forceinline__ void fft_store(const c128* X, c128* base, long stride, int n, int shift, double scale,
@@ -84,7 +45,8 @@ __global__ void fft_pow2_kernel(c128* data, int inner, int inverse, int shift, d
     A[k] = base[(long)k * inner];
   }
   __syncthreads();
-  c128* X = inverse ? stockham<L, true>(A, B, tw, threadIdx.x) : stockham<L, false>(A, B, tw, threadIdx.x);
+  const int t = threadIdx.x;
+  c128* X = inverse ? fft_lds<L, true>(A, B, tw, t, t < L / 4) : fft_lds<L, false>(A, B, tw, t, t < L / 4);
   fft_store(X, base, inner, L, shift, scale, freq, x0, inverse ? 1 : -1);
 }
 
@@ -107,14 +69,6 @@ __global__ void fft_post_kernel(const c128* __restrict__ X, c128* __restrict__ o
       v = cmul(v, cmk(c, sn));
     }
     out[f] = v;
-  }
-}
-
-__global__ void twiddles_kernel(int L, c128* tw) {
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < L; k += gridDim.x * blockDim.x) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)L, &s, &c);
-    tw[k] = cmk(c, s);
   }
 }
 
@@ -149,28 +103,21 @@ extern "C" int qd_fft_axis(qd_c128* data, int outer, int n, int inner, int inver
                (long)outer * n * inner);
   hipStream_t st = (hipStream_t)stream;
   const int batch = outer * inner;
-  const bool pow2 = n >= 16 && n <= 1024 && (n & (n - 1)) == 0;
+  const bool pow2 = pow2_in_range(n);
   note_path(pow2 ? "fft_pow2" : "fft_any");
   if (pow2) {
     void* w = nullptr;
     int rc = workspace(WS_MISC, n * sizeof(c128), &w, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(twiddles_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (c128*)w);
+    hipLaunchKernelGGL(twiddle_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (c128*)w);
     QD_HIP(hipGetLastError());
     const int threads = std::max(64, n / 4);
-#define FCALL(L)                                                                                                   \
-  hipLaunchKernelGGL(fft_pow2_kernel<L>, dim3(batch), dim3(threads), 0, st, (c128*)data, inner, inverse, shift,    \
-                     scale, freq, x0, (const c128*)w)
-    switch (n) {
-      case 16: FCALL(16); break;
-      case 32: FCALL(32); break;
-      case 64: FCALL(64); break;
-      case 128: FCALL(128); break;
-      case 256: FCALL(256); break;
-      case 512: FCALL(512); break;
-      case 1024: FCALL(1024); break;
-    }
-#undef FCALL
+    const bool hit = dispatch_int<16, 32, 64, 128, 256, 512, 1024>(n, [&](auto L) {
+      hipLaunchKernelGGL(fft_pow2_kernel<decltype(L)::value>, dim3(batch), dim3(threads), 0, st, (c128*)data, inner,
+                         inverse, shift, scale, freq, x0, (const c128*)w);
+      return true;
+    });
+    QD_CHECK_ARG(hit, "qd_fft_axis: internal: no kernel for n = %d", n);
     QD_HIP(hipGetLastError());
     return QD_OK;
   }

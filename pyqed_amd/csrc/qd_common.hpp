@@ -193,4 +193,19 @@ struct SnapSink {
 int spo_observer_check(const char* who, const int* dims, int ndim, int ns, long B, const double* const x[3],
                        const void* rdm, const void* mom);
 
+// The split-operator runs that cross files.  spo_gen.hip: every grid the specialised power-of-two kernels of spo.hip
+// do not cover (D dims, any size), its 1D form, and the matrix exponentials of qd_spo_expm.
+int spo_generic_run(c128* psi, const c128* expVh, const c128* expV, const c128* expK, const c128* expKy,
+                    const int* dims, int D, int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st);
+int spo1d_generic_run(c128* psi, const c128* expV, const c128* expVh, const c128* expK, int nx, int B, int nt,
+                      int nout, c128* snap, hipStream_t st);
+int spo_expm_run(const void* v, int v_complex, int herm, long npts, int ns, double dt, c128* expV, c128* expVh,
+                 hipStream_t st);
+// spo.hip: 64^3 grids on the register transforms (three separable passes per step)
+int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout,
+                   const SnapSink& snap, hipStream_t st);
+// spo_dense.hip: qd_spo3_run_axes with its snapshot store behind a sink
+int spo3_axes_sink(c128* psi, const c128* expVh, const c128* mx, const c128* my, const c128* mz, int nx, int ny, int nz,
+                   int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st);
+
 }  // namespace qd

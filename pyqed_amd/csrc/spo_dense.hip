@@ -166,10 +166,6 @@ int run_axes(c128* psi, const c128* Vh, const c128* const m[3], const int d[3], 
 
 }  // namespace
 
-// spo.hip: 64^3 grids on the register transforms (three separable passes per step)
-int spo3_sep64_run(c128* psi, const c128* Vh, const c128* const m[3], int ns, int nsteps, int nout,
-                   const SnapSink& snap, hipStream_t st);
-
 // qd_spo3_run_axes with its snapshot store behind a sink (qd_common.hpp)
 int spo3_axes_sink(c128* psi, const c128* expVh, const c128* mx, const c128* my, const c128* mz, int nx, int ny, int nz,
                    int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st) {

@@ -68,7 +68,7 @@ def test_spo1d_any_size_plans(n, plan):
 
 # ---------------------------------------------------------------- SPO2
 def spo2_path(nx, ny, ns):
-    """qd_spo2_run_ex's dispatch rule (spo.hip): the power-of-two kernels take 16 <= L <= 1024, ns <= 8 with
+    """qd_spo2_run_ex's dispatch rule (spo_plan.hpp): the power-of-two kernels take 16 <= L <= 1024, ns <= 8 with
     ns (ny / 4) <= 256 and ns (nx / 4) <= 256 and both passes within the LDS."""
     p2 = lambda n: 16 <= n <= 1024 and n & (n - 1) == 0
     lds = max((ny + 2 * ns * ny) * 16, (nx + 4 * ns * nx) * 16)
@@ -136,21 +136,44 @@ def test_spo2_jacobi_any_size_grid():
 
 
 # ---------------------------------------------------------------- SPO3
-@pytest.mark.parametrize("dims,path", [((16, 64, 32), "spo3_pow2"), ((7, 67, 5), "spo_any")])
+# (nx, ny, nz[, ns = 2]) and the paths the run must note.  Beyond the first two: for every pass family and tile width
+# the SPO3 plans reach (the set in test_spo_plan_host.py), the smallest grid that takes it.
+SPO3_CASES = [((16, 64, 32), "spo3_pow2"), ((7, 67, 5), "spo_any"),
+              ((16, 64, 16, 1), "spo3_row_fast+spo3_mid64_c4+spo3_col_fast_c2"),
+              ((16, 16, 16, 1), "spo3_row_fast+spo3_mid_fast_c4+spo3_col_fast_c2"),
+              ((64, 16, 64, 2), "spo3_row64+spo3_mid_fast_c8+spo3_col64_c4"),
+              ((64, 16, 128, 1), "spo3_row_fast+spo3_mid_fast_c8+spo3_col64_c8"),
+              ((32, 16, 128, 2), "spo3_row_fast+spo3_mid_fast_c8+spo3_col_fast_c4"),
+              ((16, 16, 256, 2), "spo3_row_q16+spo3_mid_fast_c8+spo3_col_fast_c4"),
+              ((32, 16, 256, 1), "spo3_row_q16+spo3_mid_fast_c8+spo3_col_fast_c8"),
+              ((32, 16, 64, 4), "spo3_row_lds+spo3_mid_fast_c8+spo3_col_lds_c2"),
+              ((64, 16, 64, 4), "spo3_row_lds+spo3_mid_fast_c16+spo3_col_lds_c4"),
+              ((16, 128, 16, 1), "spo3_row_fast+spo3_mid_lds_c4+spo3_col_fast_c2"),
+              ((16, 256, 16, 1), "spo3_row_fast+spo3_mid_lds_c4+spo3_col_fast_c2"),
+              ((16, 128, 64, 8), "spo3_row_lds+spo3_mid_lds_c8+spo3_col_lds_c2"),
+              ((16, 64, 64, 8), "spo3_row_lds+spo3_mid64_c8+spo3_col_lds_c2"),
+              ((16, 64, 128, 8), "spo3_row_lds+spo3_mid64_c16+spo3_col_lds_c2"),
+              ((256, 16, 16, 2), "spo3_row_fast+spo3_mid_fast_c8+spo3_col_q16")]
+
+
+@pytest.mark.parametrize("dims,path", SPO3_CASES)
 def test_spo3_fft_passes(dims, path, monkeypatch):
     from oracle import spo as osp
     from pyqed_amd import SPO3
+    dims, ns = dims[:3], (dims[3:] or (2,))[0]
     x, y, z = (np.linspace(-l, l, n) for l, n in zip((6.0, 5.0, 5.5), dims))
     X, Y, Z = np.meshgrid(x, y, z, indexing="ij")
-    surfaces = [0.5 * ((X + 1) ** 2 + Y ** 2 + Z ** 2), 0.5 * ((X - 1) ** 2 + Y ** 2 + Z ** 2)]
-    sol = SPO3(x, y, z, masses=[1.0, 1.2, 0.9], nstates=2)
-    sol.set_DPES(surfaces, [[[0, 1], 0.2 * X]])
+    # ns displaced wells (ns = 2: centres -1 and 1), neighbours coupled
+    surfaces = [0.5 * ((X - c) ** 2 + Y ** 2 + Z ** 2) for c in (np.linspace(-1, 1, ns) if ns > 1 else (0.0,))]
+    sol = SPO3(x, y, z, masses=[1.0, 1.2, 0.9], nstates=ns)
+    sol.set_DPES(surfaces, [[[a, a + 1], 0.2 * X] for a in range(ns - 1)])
     monkeypatch.setattr(SPO3, "kinetic_path", "fft")
-    psi0 = white(dims + (2,), 400 + sum(dims))
+    psi0 = white(dims + (ns,), 400 + sum(dims))
     took("")
     r = sol.run(psi0=psi0, dt=DT, nt=NT, nout=NOUT)
     got = took("")[1]
-    assert path in got, (path, got)
+    for name in path.split("+"):
+        assert name in got, (name, got)
     pl, fin = osp.spo3_run(sol.exp_V_half, sol.exp_K, psi0, NT, NOUT)
     assert len(r.psilist) == len(pl) == NT // NOUT
-    check(f"SPO3 {dims}", [(r.psi, fin)] + [(r.psilist[k], pl[k]) for k in range(len(pl))], dims)
+    check(f"SPO3 {dims} x {ns}", [(r.psi, fin)] + [(r.psilist[k], pl[k]) for k in range(len(pl))], dims)
