@@ -589,6 +589,27 @@ int qd_spo3_run_observed(qd_c128* psi, const qd_c128* expVh, const qd_c128* expK
                          void* stream);
 
 /*
+ * Wavepackets in curvilinear coordinates (pyqed/wpd.py:1783-1940: adiabatic_2d with
+ * coords='curvilinear', KEO, PEO, hpsi): K psi = 1/2 sum_rs p_r G_rs(x, y) p_s psi with a
+ * position-dependent real 2 x 2 metric G (all four entries are read, no symmetry assumed).
+ * nx, ny powers of two in [16, 1024] run the fused column / row kernels; every other shape
+ * (an axis of length 1 included) the any-length transforms.  B nx ny < 2^31.
+ *
+ * out = K psi (v == NULL) or (K + v) psi.  psi, out [B][nx][ny] complex128, out must not alias psi;
+ * G [nx][ny][2][2] float64; v [nx][ny] complex128 or NULL; kx [nx], ky [ny] float64 (any multipliers, as the
+ * reference's hpsi(psi, kx, ky, v, G) takes them).
+ */
+int qd_wp2_gmat_apply(const qd_c128* psi, int B, const double* G, const qd_c128* v, const double* kx,
+                      const double* ky, int nx, int ny, qd_c128* out, void* stream);
+
+/*
+ * nsteps Horner-RK4 steps of i dpsi/dt = (K + v) psi, psi [B][nx][ny] in place; snap [B][nsteps/nout][nx][ny]
+ * (state after steps nout, 2 nout, ...) or NULL.  phys.rk4 (phys.py:1051-1064) up to rounding.  nsteps == 0: no-op.
+ */
+int qd_wp2_gmat_rk4(qd_c128* psi, int B, const double* G, const qd_c128* v, const double* kx, const double* ky,
+                    int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap, void* stream);
+
+/*
  * RK4 with a dense Liouville-space generator, d v/dt = L v (B vectors).
  * Replaces the csr GEMV loop of pyqed/oqs.py:436-463 (_redfield + rhs) for any
  * dense superoperator.  L [N2][N2], v [B][N2] in/out (row-major vec(rho)),

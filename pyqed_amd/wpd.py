@@ -6,6 +6,8 @@ ns <= 2, a matrix exponential up to ns = 256).
 Every propagation step runs in libqdyn (qd_spo1d_run / qd_spo2_run_ex / qd_spo3_run).
 Populations, mean positions and the electronic reduced density matrix are reduced on the device
 (qd_spo_observe), after the run from states or inside it (run(..., observe=...), qd_spo*_run_observed).
+Curvilinear coordinates (wpd.py:1783-1940: adiabatic_2d, KEO, PEO, hpsi) apply the G-matrix kinetic operator and run
+its RK4 steps in libqdyn (qd_wp2_gmat_apply / qd_wp2_gmat_rk4).
 """
 from __future__ import annotations
 
@@ -892,3 +894,139 @@ class SPO3(_PointPropagators):
             r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
             r.xAve = [mom[:, d].sum(axis=-1) for d in range(3)]
         return r
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Curvilinear coordinates: the G-matrix kinetic operator and its RK4 propagation (wpd.py:1783-1940)
+
+def _is_complex_nonzero(a):
+    """A non-zero imaginary part anywhere.  Host data is checked on the host; a complex tensor that already lives on
+    the device is reduced there (the one check that touches the device before a refusal)."""
+    if isinstance(a, torch.Tensor):
+        return a.is_complex() and bool((a.imag != 0).any())
+    return np.iscomplexobj(a) and bool(np.any(np.imag(a) != 0))
+
+
+def _gmat_check(psi, G, v, nkx, nky):
+    """Shape and type checks of a curvilinear call, before any device call for ndarray and host-tensor operands (a
+    complex G held on the device is tested there).  Returns (nx, ny, batched)."""
+    shape = tuple(psi.shape) if isinstance(psi, torch.Tensor) else np.shape(psi)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"psi must be [nx, ny] or a batch [B, nx, ny]; got {shape}")
+    nx, ny = int(shape[-2]), int(shape[-1])
+    if G is None:
+        raise ValueError("curvilinear coordinates need the metric G [nx, ny, 2, 2]")
+    gshape = tuple(G.shape) if isinstance(G, torch.Tensor) else np.shape(G)
+    if gshape != (nx, ny, 2, 2):
+        raise ValueError(f"G must be {(nx, ny, 2, 2)} for psi {shape}; got {gshape}")
+    if _is_complex_nonzero(G):
+        raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
+    if v is not None:
+        vshape = tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)
+        if vshape != (nx, ny):
+            raise ValueError(f"v must be {(nx, ny)} for psi {shape}; got {vshape}")
+    if (nkx, nky) != (nx, ny):
+        raise ValueError(f"kx, ky have lengths {(nkx, nky)}; psi {shape} needs {(nx, ny)}")
+    return nx, ny, len(shape) == 3
+
+
+def _gmat_dev(psi, G, v, kx, ky):
+    """Device operands: psi [B, nx, ny] (a contiguous complex128 device tensor is used in place, not copied), G float64,
+    v complex128 or None, kx, ky float64."""
+    dev = psi.device if isinstance(psi, torch.Tensor) and psi.device.type == "cuda" else default_device()
+    _lib.ensure_device(dev)
+    t = psi.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(psi, torch.Tensor) \
+        else _dev_c128(psi, dev)
+    if t.dim() == 2:
+        t = t[None]
+    if isinstance(G, torch.Tensor):
+        Gd = (G.real if G.is_complex() else G).to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        Gd = _dev_f64(np.real(G), dev)
+    vd = None
+    if v is not None:
+        vd = v.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(v, torch.Tensor) else _dev_c128(v, dev)
+    f64 = lambda k: k.to(device=dev, dtype=torch.float64).contiguous() if isinstance(k, torch.Tensor) \
+        else _dev_f64(k, dev)
+    return dev, t, Gd, vd, f64(kx), f64(ky)
+
+
+def _gmat_apply(psi, kx, ky, v, G):
+    """(K + v) psi on the device (qd_wp2_gmat_apply); returns a device tensor shaped like psi."""
+    nx, ny, batched = _gmat_check(psi, G, v, len(kx), len(ky))
+    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi, G, v, kx, ky)
+    out = torch.empty_like(t)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_wp2_gmat_apply(t.data_ptr(), int(t.shape[0]), Gd.data_ptr(), _lib.ptr(vd), kxd.data_ptr(),
+                                           kyd.data_ptr(), nx, ny, out.data_ptr(), _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_wp2_gmat_apply")
+    return out if batched else out[0]
+
+
+def _like_input(out, psi):
+    """The device result where the input lives: an ndarray for an ndarray, a tensor on psi's device for a tensor."""
+    return out.to(psi.device) if isinstance(psi, torch.Tensor) else out.cpu().numpy()
+
+
+def KEO(psi, kx, ky, G):
+    """wpd.py:1861-1915: K psi = 1/2 sum_rs p_r G_rs p_s psi, with p_x psi = ifft2(kx fft2 psi) (the transform along
+    the other axis cancels: one line transform pair per derivative).  G [nx, ny, 2, 2] real, all four entries read.
+    Extensions: psi may carry a leading batch axis [B, nx, ny]; a tensor in gives a tensor out on the same device (a
+    device tensor stays on the device, a host tensor comes back to the host)."""
+    return _like_input(_gmat_apply(psi, kx, ky, None, G), psi)
+
+
+def PEO(psi, v):
+    """wpd.py:1917-1933: v psi."""
+    return v * psi
+
+
+def hpsi(psi, kx, ky, v, G):
+    """wpd.py:1935-1940: -1j (K psi + v psi), one library call for K psi + v psi; v real or complex."""
+    return _like_input(-1j * _gmat_apply(psi, kx, ky, v, G), psi)
+
+
+def curvilinear_run(x, y, psi0s, v, G, dt, nt, nout=1):
+    """Extension: RK4 propagation of B wavepackets psi0s [B, nx, ny] (or one, [nx, ny]) in curvilinear coordinates on
+    one potential and metric (qd_wp2_gmat_rk4, one launch per pass for the whole batch).  Runs (nt // nout) nout steps,
+    as SPO2.run_batch; returns (final states [B, nx, ny], snapshots [B, nt // nout, nx, ny]) as device tensors,
+    whatever psi0s was (ndarray, host or device tensor).  psi0s is not modified."""
+    if nout < 1 or nt < 0:
+        raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
+    nx, ny, _ = _gmat_check(psi0s, G, v, len(x), len(y))
+    kx = 2. * np.pi * fftfreq(nx, interval(x)) if nx > 1 else np.zeros(1)
+    ky = 2. * np.pi * fftfreq(ny, interval(y)) if ny > 1 else np.zeros(1)
+    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi0s, G, v, kx, ky)
+    psi = t.clone()
+    B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
+    snap = torch.empty((B, nsnap, nx, ny), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_wp2_gmat_rk4(psi.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd), kxd.data_ptr(),
+                                         kyd.data_ptr(), nx, ny, float(dt), nsnap * int(nout), int(nout),
+                                         snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_wp2_gmat_rk4")
+    return psi, snap
+
+
+def adiabatic_2d(x, y, psi0, v, dt, Nt=0, coords='linear', mass=None, G=None):
+    """wpd.py:1783-1859, coords='curvilinear': Nt RK4 steps (phys.rk4, phys.py:1051-1064, in Horner form) of
+    i dpsi/dt = (K + v) psi with hpsi (wpd.py:1935-1940); kx, ky = 2 pi fftfreq(n, dx) as the reference builds them.
+    Returns the final psi (psi0 is untouched; Nt=0 returns a copy); `mass` is unused on this branch, as there.
+
+    coords='linear' raises NotImplementedError: the reference's branch fails in x_evolve_2d (wpd.py:1826, an einsum
+    with 4-index subscripts on a 2-D array) before its first step, and a broken path is not reproduced as a failure;
+    SPO2(x, y, mass, nstates=1) is the split-operator propagation on one surface.  Any other coords raises ValueError
+    (the reference silently returns a copy of psi0).
+
+    Extensions: psi0 may carry a leading batch axis [B, nx, ny]; a tensor in gives a tensor out on the same device.
+    The refusals below come before any device call, but for a complex G that already lives on the device, whose
+    imaginary part is tested there."""
+    if coords == 'linear':
+        raise NotImplementedError(
+            "adiabatic_2d(coords='linear'): the reference's branch is broken (x_evolve_2d raises ValueError, "
+            "wpd.py:1826); use SPO2(x, y, mass, nstates=1) for split-operator dynamics on one surface")
+    if coords != 'curvilinear':
+        raise ValueError(f"coords = {coords!r}; adiabatic_2d knows 'curvilinear' (and refuses 'linear')")
+    _, _, batched = _gmat_check(psi0, G, v, len(x), len(y))
+    psi, _ = curvilinear_run(x, y, psi0, v, G, dt, int(Nt), 1)
+    return _like_input(psi if batched else psi[0], psi0)
