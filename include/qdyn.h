@@ -610,6 +610,20 @@ int qd_wp2_gmat_rk4(qd_c128* psi, int B, const double* G, const qd_c128* v, cons
                     int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap, void* stream);
 
 /*
+ * The same on ns coupled surfaces: i dpsi_a/dt = K psi_a + sum_b V_ab(x, y) psi_b, K as above and identical on every
+ * state.  The states are planes: psi, out [B][ns][nx][ny], V [ns][ns][nx][ny] complex128 (V[a][b] the plane of V_ab;
+ * no Hermiticity assumed, so an absorbing -i eta diagonal works) or NULL for no potential, snap
+ * [B][nsteps/nout][ns][nx][ny] or NULL.  Any ns >= 1; B ns nx ny < 2^31 and ns ns nx ny < 2^31.  The other arguments,
+ * the shape dispatch and the rules (out must not alias psi; nsteps == 0: no-op) are those of qd_wp2_gmat_apply /
+ * qd_wp2_gmat_rk4, of which ns = 1 is the same arithmetic; the power-of-two column tile is chosen for B ns members.
+ * Asynchronous on `stream` and capturable; scratch from the arena (rk4: five states for ns > 1, four for ns = 1).
+ */
+int qd_wp2_gmat_ms_apply(const qd_c128* psi, int B, int ns, const double* G, const qd_c128* V, const double* kx,
+                         const double* ky, int nx, int ny, qd_c128* out, void* stream);
+int qd_wp2_gmat_ms_rk4(qd_c128* psi, int B, int ns, const double* G, const qd_c128* V, const double* kx,
+                       const double* ky, int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap, void* stream);
+
+/*
  * RK4 with a dense Liouville-space generator, d v/dt = L v (B vectors).
  * Replaces the csr GEMV loop of pyqed/oqs.py:436-463 (_redfield + rhs) for any
  * dense superoperator.  L [N2][N2], v [B][N2] in/out (row-major vec(rho)),

@@ -19,6 +19,15 @@
 //   wp2_gmat_any    every other shape: fft_lines along each axis and element-wise kernels between; where fft_lines
 //                   leaves four-step order the k table is applied through that order.
 // No atomics; a member's result is a function of the shape alone.
+//
+// Coupled surfaces (qd_wp2_gmat_ms_apply / qd_wp2_gmat_ms_rk4, noted as wp2_gmat_ms): i dpsi_a/dt = K psi_a +
+// sum_b V_ab psi_b, K the same on every state.  The states are planes, psi [B][ns][nx][ny], so both paths above run
+// unchanged on B ns members (the tile rule counts B ns) and only the last kernel of a stage, which adds
+// sum_b V_ab y_b, knows ns.  That kernel reads the planes b != a of y, which other workgroups of the same launch
+// write when y is updated in place, so for ns > 1 the stages ping-pong between two y arrays (psi -> y -> y' -> y ->
+// psi: five state-sized scratch arrays instead of four).  The alternative, one workgroup owning all ns planes of its
+// rows, would tie the row tile and its LDS to ns; the extra array costs memory only.  The single-surface entry
+// points are the ns = 1 case of the same code.
 #include <atomic>
 
 #include "spo_plan.hpp"
@@ -28,13 +37,14 @@ namespace qd {
 namespace {
 
 struct GmatArgs {
-  int B, nx, ny;
+  int B, ns, nx, ny;   // B ns members: the states of a coupled system are planes [B][ns][nx][ny]
   const double* G;
-  const c128* v;
+  const c128* v;       // [ns][ns][nx][ny]
   const double *kx, *ky;
   hipStream_t st;
   long npts() const { return (long)nx * ny; }
-  long total() const { return (long)B * nx * ny; }
+  long members() const { return (long)B * ns; }
+  long total() const { return members() * nx * ny; }
 };
 
 int check_args(const char* who, const void* psi, int B, const void* G, const void* kx, const void* ky, int nx, int ny) {
@@ -42,6 +52,16 @@ int check_args(const char* who, const void* psi, int B, const void* G, const voi
   QD_CHECK_ARG(B >= 1 && nx >= 1 && ny >= 1, "%s: B=%d nx=%d ny=%d must be >= 1", who, B, nx, ny);
   QD_CHECK_ARG((double)B * nx * ny < 2147483648.0, "%s: B nx ny = %.0f points, must be < 2^31", who,
                (double)B * nx * ny);
+  return QD_OK;
+}
+
+int check_args_ms(const char* who, const void* psi, int B, int ns, const void* G, const void* kx, const void* ky,
+                  int nx, int ny) {
+  QD_CHECK_ARG(psi && G && kx && ky, "%s: null pointer (psi, G, kx and ky must be non-null)", who);
+  QD_CHECK_ARG(B >= 1 && ns >= 1 && nx >= 1 && ny >= 1, "%s: B=%d ns=%d nx=%d ny=%d must be >= 1", who, B, ns, nx, ny);
+  QD_CHECK_ARG((double)B * ns * nx * ny < 2147483648.0 && (double)ns * ns * nx * ny < 2147483648.0,
+               "%s: B ns nx ny = %.0f, ns ns nx ny = %.0f points, must be < 2^31", who, (double)B * ns * nx * ny,
+               (double)ns * ns * nx * ny);
   return QD_OK;
 }
 
@@ -88,7 +108,7 @@ struct Pow2 {
     if (a.nx >= WPG_WIDE_MIN_NX) {
       int cus = 0;
       QD_TRY(device_cus(&cus));
-      wide = (long)a.B * (a.ny / WPG_WIDE_C) >= cus;
+      wide = a.members() * (a.ny / WPG_WIDE_C) >= cus;
     }
     if (wide) QD_TRY(a.nx == 512 ? col_wide_ready<512>() : col_wide_ready<1024>());
     note_path(wide ? "wp2_gmat_col_wide" : "wp2_gmat_col_narrow");
@@ -122,7 +142,7 @@ struct Pow2 {
       auto launch = [&](auto C_) {
         constexpr int C = decltype(C_)::value;
         constexpr size_t lds = wpg_col_lds(L, C);
-        hipLaunchKernelGGL((wp2_gmat_col_kernel<L, C>), dim3((unsigned)((long)a.B * (a.ny / C))), dim3(C * L / 4), lds,
+        hipLaunchKernelGGL((wp2_gmat_col_kernel<L, C>), dim3((unsigned)(a.members() * (a.ny / C))), dim3(C * L / 4), lds,
                            a.st, y, dy, a.G, (const c128*)twx, (const double*)kxs, a.ny, u, phy);
       };
       if (wide) launch(int_c<wpg_col_wide(L)>{});
@@ -139,9 +159,9 @@ struct Pow2 {
     const bool hit = dispatch_int<16, 32, 64, 128, 256, 512, 1024>(a.ny, [&](auto L_) {
       return dispatch_int<WPG_PRO, WPG_APPLY, WPG_STAGE>(mode, [&](auto M_) {
         constexpr int L = decltype(L_)::value, R = wpg_row_r(L);
-        hipLaunchKernelGGL((wp2_gmat_row_kernel<L, decltype(M_)::value>), dim3((unsigned)((long)a.B * (a.nx / R))),
+        hipLaunchKernelGGL((wp2_gmat_row_kernel<L, decltype(M_)::value>), dim3((unsigned)(a.members() * (a.nx / R))),
                            dim3(R * L / 4), 0, a.st, phy, u, ys, psi, a.v, (const c128*)twy, (const double*)kys, a.nx,
-                           coef, ynew, dy, snap, sstride);
+                           a.ns, coef, ynew, dy, snap, sstride);
         return true;
       });
     });
@@ -167,7 +187,7 @@ int pow2_apply(const GmatArgs& a, const c128* psi, c128* out) {
 struct AnyGrid {
   GmatArgs a;
   double *kxs, *kys;
-  c128 *t1, *t2;   // transform scratch, [B][nx][ny] each
+  c128 *t1, *t2;   // transform scratch, one state each
 
   int prepare() {
     void* w = nullptr;
@@ -186,7 +206,7 @@ struct AnyGrid {
   // dst = D_axis src (axis 0: x, 1: y); dst may be src
   int deriv(const c128* src, int axis, c128* dst) const {
     const long n = a.total();
-    const long O = axis ? (long)a.B * a.nx : a.B, I = axis ? 1 : a.ny;
+    const long O = axis ? a.members() * a.nx : a.members(), I = axis ? 1 : a.ny;
     const int L = axis ? a.ny : a.nx;
     const double* ks = axis ? kys : kxs;
     QD_TRY(copy_device(t1, src, (size_t)n * sizeof(c128), a.st));
@@ -207,7 +227,8 @@ struct AnyGrid {
     return QD_OK;
   }
 
-  // ynew = (K + v) ys (psi null) or psi - i coef (K + v) ys; b0..b2: three [B][nx][ny] buffers
+  // ynew = (K + v) ys (psi null) or psi - i coef (K + v) ys; b0..b2: three state-sized buffers; ynew may be ys for
+  // ns = 1 alone
   int stage(const c128* ys, const c128* psi, double coef, c128* ynew, c128* snap, size_t sstride, c128* b0, c128* b1,
             c128* b2) const {
     const long n = a.total();
@@ -218,13 +239,65 @@ struct AnyGrid {
     QD_TRY(deriv(b0, 0, b2));
     QD_TRY(deriv(b1, 1, b0));
     hipLaunchKernelGGL(wpg_combine_kernel, dim3(grid_for(n)), dim3(256), 0, a.st, (const c128*)b2, (const c128*)b0, ys,
-                       psi, a.v, n, a.npts(), coef, ynew, snap, sstride);
+                       psi, a.v, n, a.npts(), a.ns, coef, ynew, snap, sstride);
     QD_HIP(hipGetLastError());
     return QD_OK;
   }
 };
 
 bool pow2_grid(int nx, int ny) { return pow2_in_range(nx) && pow2_in_range(ny); }
+
+// out = (K + V) psi; the caller has checked the arguments and holds the call's WsScope
+int gmat_apply(const GmatArgs& a, const c128* psi, c128* out) {
+  const bool pow2 = pow2_grid(a.nx, a.ny);
+  note_path(pow2 ? "wp2_gmat_pow2" : "wp2_gmat_any");
+  if (pow2) return pow2_apply(a, psi, out);
+  AnyGrid g{a};
+  QD_TRY(g.prepare());
+  void* w = nullptr;
+  const size_t n = (size_t)a.total();
+  QD_TRY(workspace(WS_SPO, 3 * n * sizeof(c128), &w, a.st));
+  c128* b = (c128*)w;
+  return g.stage(psi, nullptr, 0.0, out, nullptr, 0, b, b + n, b + 2 * n);
+}
+
+// nsteps >= 1 Horner-RK4 steps of psi in place, snapshots [B][nsteps / nout][ns][nx][ny]
+int gmat_rk4(const GmatArgs& a, c128* psi, double dt, int nsteps, int nout, c128* snap) {
+  hipStream_t st = a.st;
+  const size_t n = (size_t)a.total(), mpts = (size_t)a.ns * a.npts();   // points of the batch, of one member
+  const size_t sstride = (size_t)(nsteps / nout) * mpts;                // between the members' snapshot blocks
+  const double coef[4] = {dt * 0.25, dt / 3.0, dt * 0.5, dt};   // rk4_horner_coef
+  const bool pow2 = pow2_grid(a.nx, a.ny);
+  note_path(pow2 ? "wp2_gmat_pow2" : "wp2_gmat_any");
+  const bool pingpong = a.ns > 1;   // a stage reads y across planes: it must not write the array it reads
+  void* w = nullptr;
+  QD_TRY(workspace(WS_SPO, (pingpong ? 5 : 4) * n * sizeof(c128), &w, st));
+  c128 *y = (c128*)w, *s1 = y + n, *s2 = s1 + n, *s3 = s2 + n, *y2 = pingpong ? s3 + n : y;
+  Pow2 p{a};
+  AnyGrid g{a};
+  if (pow2) {
+    QD_TRY(p.prepare());
+    QD_TRY(p.row(WPG_PRO, nullptr, nullptr, psi, nullptr, 0.0, nullptr, s1, nullptr, 0));   // s1 = D_y psi
+  } else {
+    QD_TRY(g.prepare());
+  }
+  const c128* srcs[4] = {psi, y, y2, y};   // psi -> y -> y2 -> y -> psi
+  c128* dsts[4] = {y, y2, y, psi};
+  for (int step = 1; step <= nsteps; ++step) {
+    for (int s = 0; s < 4; ++s) {
+      const c128* src = srcs[s];
+      c128* dst = dsts[s];
+      c128* sp = (s == 3 && snap && step % nout == 0) ? snap + (size_t)(step / nout - 1) * mpts : nullptr;
+      if (pow2) {
+        QD_TRY(p.col(src, s1, s2, s3));                                            // s2 = u, s3 = phi_y
+        QD_TRY(p.row(WPG_STAGE, s3, s2, src, psi, coef[s], dst, s1, sp, sstride));   // s1 = D_y y_{s+1}
+      } else {
+        QD_TRY(g.stage(src, psi, coef[s], dst, sp, sstride, s1, s2, s3));
+      }
+    }
+  }
+  return QD_OK;
+}
 
 }  // namespace
 }  // namespace qd
@@ -238,57 +311,39 @@ extern "C" int qd_wp2_gmat_apply(const qd_c128* psi, int B, const double* G, con
   QD_TRY(check_args("qd_wp2_gmat_apply", psi, B, G, kx, ky, nx, ny));
   QD_CHECK_ARG(out, "qd_wp2_gmat_apply: null pointer (out must be non-null)");
   QD_CHECK_ARG((const void*)out != (const void*)psi, "qd_wp2_gmat_apply: out must not alias psi");
-  const GmatArgs a{B, nx, ny, G, (const c128*)v, kx, ky, st};
-  const bool pow2 = pow2_grid(nx, ny);
-  note_path(pow2 ? "wp2_gmat_pow2" : "wp2_gmat_any");
-  if (pow2) return pow2_apply(a, (const c128*)psi, (c128*)out);
-  AnyGrid g{a};
-  QD_TRY(g.prepare());
-  void* w = nullptr;
-  const size_t n = (size_t)a.total();
-  QD_TRY(workspace(WS_SPO, 3 * n * sizeof(c128), &w, st));
-  c128* b = (c128*)w;
-  return g.stage((const c128*)psi, nullptr, 0.0, (c128*)out, nullptr, 0, b, b + n, b + 2 * n);
+  return gmat_apply(GmatArgs{B, 1, nx, ny, G, (const c128*)v, kx, ky, st}, (const c128*)psi, (c128*)out);
 }
 
-extern "C" int qd_wp2_gmat_rk4(qd_c128* psi_, int B, const double* G, const qd_c128* v, const double* kx,
-                               const double* ky, int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap_,
+extern "C" int qd_wp2_gmat_rk4(qd_c128* psi, int B, const double* G, const qd_c128* v, const double* kx,
+                               const double* ky, int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap,
                                void* stream) {
   hipStream_t st = (hipStream_t)stream;
   WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
-  QD_TRY(check_args("qd_wp2_gmat_rk4", psi_, B, G, kx, ky, nx, ny));
+  QD_TRY(check_args("qd_wp2_gmat_rk4", psi, B, G, kx, ky, nx, ny));
   QD_CHECK_ARG(nsteps >= 0 && nout >= 1, "qd_wp2_gmat_rk4: nsteps=%d must be >= 0 and nout=%d >= 1", nsteps, nout);
   if (nsteps == 0) return QD_OK;
-  const GmatArgs a{B, nx, ny, G, (const c128*)v, kx, ky, st};
-  c128 *psi = (c128*)psi_, *snap = (c128*)snap_;
-  const size_t n = (size_t)a.total(), npts = (size_t)a.npts();
-  const size_t sstride = (size_t)(nsteps / nout) * npts;   // between the members' snapshot blocks
-  const double coef[4] = {dt * 0.25, dt / 3.0, dt * 0.5, dt};   // rk4_horner_coef
-  const bool pow2 = pow2_grid(nx, ny);
-  note_path(pow2 ? "wp2_gmat_pow2" : "wp2_gmat_any");
-  void* w = nullptr;
-  QD_TRY(workspace(WS_SPO, 4 * n * sizeof(c128), &w, st));
-  c128 *y = (c128*)w, *s1 = y + n, *s2 = s1 + n, *s3 = s2 + n;
-  Pow2 p{a};
-  AnyGrid g{a};
-  if (pow2) {
-    QD_TRY(p.prepare());
-    QD_TRY(p.row(WPG_PRO, nullptr, nullptr, psi, nullptr, 0.0, nullptr, s1, nullptr, 0));   // s1 = D_y psi
-  } else {
-    QD_TRY(g.prepare());
-  }
-  for (int step = 1; step <= nsteps; ++step) {
-    for (int s = 0; s < 4; ++s) {
-      const c128* src = s == 0 ? psi : y;
-      c128* dst = s == 3 ? psi : y;
-      c128* sp = (s == 3 && snap && step % nout == 0) ? snap + (size_t)(step / nout - 1) * npts : nullptr;
-      if (pow2) {
-        QD_TRY(p.col(src, s1, s2, s3));                                            // s2 = u, s3 = phi_y
-        QD_TRY(p.row(WPG_STAGE, s3, s2, src, psi, coef[s], dst, s1, sp, sstride));   // s1 = D_y y_{s+1}
-      } else {
-        QD_TRY(g.stage(src, psi, coef[s], dst, sp, sstride, s1, s2, s3));
-      }
-    }
-  }
-  return QD_OK;
+  return gmat_rk4(GmatArgs{B, 1, nx, ny, G, (const c128*)v, kx, ky, st}, (c128*)psi, dt, nsteps, nout, (c128*)snap);
+}
+
+extern "C" int qd_wp2_gmat_ms_apply(const qd_c128* psi, int B, int ns, const double* G, const qd_c128* V,
+                                    const double* kx, const double* ky, int nx, int ny, qd_c128* out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_TRY(check_args_ms("qd_wp2_gmat_ms_apply", psi, B, ns, G, kx, ky, nx, ny));
+  QD_CHECK_ARG(out, "qd_wp2_gmat_ms_apply: null pointer (out must be non-null)");
+  QD_CHECK_ARG((const void*)out != (const void*)psi, "qd_wp2_gmat_ms_apply: out must not alias psi");
+  note_path("wp2_gmat_ms");
+  return gmat_apply(GmatArgs{B, ns, nx, ny, G, (const c128*)V, kx, ky, st}, (const c128*)psi, (c128*)out);
+}
+
+extern "C" int qd_wp2_gmat_ms_rk4(qd_c128* psi, int B, int ns, const double* G, const qd_c128* V, const double* kx,
+                                  const double* ky, int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap,
+                                  void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_TRY(check_args_ms("qd_wp2_gmat_ms_rk4", psi, B, ns, G, kx, ky, nx, ny));
+  QD_CHECK_ARG(nsteps >= 0 && nout >= 1, "qd_wp2_gmat_ms_rk4: nsteps=%d must be >= 0 and nout=%d >= 1", nsteps, nout);
+  if (nsteps == 0) return QD_OK;
+  note_path("wp2_gmat_ms");
+  return gmat_rk4(GmatArgs{B, ns, nx, ny, G, (const c128*)V, kx, ky, st}, (c128*)psi, dt, nsteps, nout, (c128*)snap);
 }

@@ -1,4 +1,5 @@
-// wp_gmat_kernels.hpp — kernels of the curvilinear (G-matrix) wavepacket propagator (wp_gmat.hip), psi [B][nx][ny].
+// wp_gmat_kernels.hpp — kernels of the curvilinear (G-matrix) wavepacket propagator (wp_gmat.hip), psi [B][nx][ny]
+// (on coupled surfaces [B][ns][nx][ny], below).
 //
 //   D_x f = IFFT_x(kx FFT_x f)     D_y f = IFFT_y(ky FFT_y f)      (1/n folded into the k tables)
 //   phi_x = Gxx D_x y + Gxy D_y y   phi_y = Gyx D_x y + Gyy D_y y
@@ -9,6 +10,11 @@
 //                                  u = D_x phi_x and phi_y out
 //   row pass (y, contiguous axis): R whole rows; D_y phi_y, H y, the Horner update, and D_y of the new state
 // Any other grid: element-wise kernels around fft_lines (qd_common.hpp).
+//
+// Coupled surfaces: psi [B][ns][nx][ny], the states as planes, so every pass sees B ns members; the potential
+// V [ns][ns][nx][ny], and v y of plane a becomes sum_b V_ab y_b (b ascending from V_a0 y_0, added to the kinetic half
+// last).  The sum reads every plane of the member at the thread's own points: with ns > 1 the array a stage writes
+// must not be the one it reads there (wp_gmat.hip ping-pongs y).  ns = 1 is the single-surface arithmetic.
 #pragma once
 
 #include "spo_fft_pow2.hpp"
@@ -25,6 +31,17 @@ constexpr int wpg_col_c(int L) { return L <= 64 ? 16 : 1024 / L; }
 constexpr int WPG_WIDE_MIN_NX = 512, WPG_WIDE_C = 4;
 constexpr int wpg_col_wide(int L) { return L >= WPG_WIDE_MIN_NX ? WPG_WIDE_C : wpg_col_c(L); }
 constexpr size_t wpg_col_lds(int L, int C) { return (size_t)(L + 2 * C * (L + 1)) * sizeof(c128) + L * sizeof(double); }
+
+// V y with its fused multiply-adds written out.  The single-surface kernels formed this product with cmul and took the
+// compiler's contraction of it, which chose the fused product of the imaginary part differently in the row pass and in
+// the any-grid kernel; both choices are spelled here so that those entry points keep their bits whatever a compiler
+// contracts around a loop over states.
+__device__ __forceinline__ c128 wpg_vy_row(c128 v, c128 y) {
+  return cmk(fma(v.re, y.re, -(v.im * y.im)), fma(v.im, y.re, v.re * y.im));
+}
+__device__ __forceinline__ c128 wpg_vy_any(c128 v, c128 y) {
+  return cmk(fma(v.re, y.re, -(v.im * y.im)), fma(v.re, y.im, v.im * y.re));
+}
 
 // ks[k] = k[k] / n: the multiplier of a forward / inverse transform pair
 __global__ void wpg_ktable_kernel(const double* k, int n, double* ks) {
@@ -106,43 +123,56 @@ __global__ __launch_bounds__(C * L / 4) void wp2_gmat_col_kernel(const c128* y, 
   }
 }
 
-// Row pass over rows r0 .. r0 + R - 1 of member m (blockIdx.x = m (nx / R) + r0 / R), L = ny.
+// Row pass over rows r0 .. r0 + R - 1 of plane a of member m (blockIdx.x = (m ns + a) (nx / R) + r0 / R), L = ny.
 //   WPG_PRO:   dy = D_y ys
-//   WPG_APPLY: ynew = 1/2 (u + D_y phy) + v ys                                  (v null: no potential)
-//   WPG_STAGE: ynew = psi - i coef (1/2 (u + D_y phy) + v ys), also to snap when given; dy = D_y ynew
-// ynew may be ys or psi: a thread reads the points it writes before it writes them.
+//   WPG_APPLY: ynew = 1/2 (u + D_y phy) + sum_b V_ab ys_b                        (v null: no potential)
+//   WPG_STAGE: ynew = psi - i coef (1/2 (u + D_y phy) + sum_b V_ab ys_b), also to snap when given; dy = D_y ynew
+// ynew may be psi (read at the thread's own plane and points only).  ynew may be ys for ns = 1 alone: a thread reads
+// the points it writes before it writes them, but the planes b != a of ys belong to other workgroups.
 enum WpgRowMode { WPG_PRO = 0, WPG_APPLY = 1, WPG_STAGE = 2 };
 
 template <int L, int MODE>
 __global__ __launch_bounds__(wpg_row_r(L) * L / 4) void wp2_gmat_row_kernel(const c128* phy, const c128* u,
                                                                             const c128* ys, const c128* psi,
                                                                             const c128* v, const c128* twy,
-                                                                            const double* kys, int nx, double coef,
-                                                                            c128* ynew, c128* dy, c128* snap,
-                                                                            size_t sstride) {
+                                                                            const double* kys, int nx, int ns,
+                                                                            double coef, c128* ynew, c128* dy,
+                                                                            c128* snap, size_t sstride) {
   constexpr int R = wpg_row_r(L), BD = R * L / 4;
   __shared__ c128 tw[L], A[R * L], Bf[R * L];
   __shared__ double ks[L];
   const int tid = threadIdx.x, nblk = nx / R;
-  const int m = blockIdx.x / nblk;
+  const int mp = blockIdx.x / nblk, sa = mp % ns;            // plane mp = m ns + sa
+  const size_t npts = (size_t)nx * L;
   const size_t vo = (size_t)(blockIdx.x % nblk) * R * L;   // the tile is R L contiguous points
-  const size_t po = (size_t)m * nx * L + vo;
-  c128 yv[4], ph[4], uv[4], vv[4], ps[4];
+  const size_t po = (size_t)mp * npts + vo;
+  c128 ph[4], uv[4], vy[4], ps[4];   // ph: phy, or ys itself in WPG_PRO; vy: sum_b V_ab ys_b
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
     const int e = tid + n * BD;
-    yv[n] = ys[po + e];
-    ph[n] = MODE != WPG_PRO ? phy[po + e] : cmk(0, 0);
+    ph[n] = MODE != WPG_PRO ? phy[po + e] : ys[po + e];
     uv[n] = MODE != WPG_PRO ? u[po + e] : cmk(0, 0);
-    vv[n] = MODE != WPG_PRO && v ? v[vo + e] : cmk(0, 0);
     ps[n] = MODE == WPG_STAGE ? psi[po + e] : cmk(0, 0);
+    vy[n] = cmk(0, 0);
+  }
+  if (MODE != WPG_PRO && v) {
+    const c128* yb = ys + (size_t)(mp - sa) * npts + vo;   // plane 0 of this member
+    const c128* vb = v + (size_t)sa * ns * npts + vo;      // V_a0
+#pragma unroll
+    for (int n = 0; n < 4; ++n) vy[n] = wpg_vy_row(vb[tid + n * BD], yb[tid + n * BD]);
+    for (int b = 1; b < ns; ++b) {
+      yb += npts;
+      vb += npts;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) vy[n] = cadd(vy[n], wpg_vy_row(vb[tid + n * BD], yb[tid + n * BD]));
+    }
   }
   for (int k = tid; k < L; k += BD) {
     tw[k] = twy[k];
     ks[k] = kys[k];
   }
 #pragma unroll
-  for (int n = 0; n < 4; ++n) A[tid + n * BD] = MODE == WPG_PRO ? yv[n] : ph[n];
+  for (int n = 0; n < 4; ++n) A[tid + n * BD] = ph[n];
   __syncthreads();
   c128* cur = wpg_deriv<L, L, R>(A, Bf, tw, ks, tid);
   if (MODE == WPG_PRO) {
@@ -153,13 +183,13 @@ __global__ __launch_bounds__(wpg_row_r(L) * L / 4) void wp2_gmat_row_kernel(cons
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
     const int e = tid + n * BD;
-    const c128 h = cadd(cscale(cadd(uv[n], cur[e]), 0.5), cmul(vv[n], yv[n]));
+    const c128 h = cadd(cscale(cadd(uv[n], cur[e]), 0.5), vy[n]);
     if (MODE == WPG_APPLY) {
       ynew[po + e] = h;
     } else {
       const c128 yn = cadd(ps[n], cscale(cmulmi(h), coef));
       ynew[po + e] = yn;
-      if (snap) snap[(size_t)m * sstride + vo + e] = yn;
+      if (snap) snap[(size_t)(mp / ns) * sstride + (size_t)sa * npts + vo + e] = yn;
       cur[e] = yn;   // the slot this thread read
     }
   }
@@ -196,20 +226,29 @@ __global__ void wpg_gprod_kernel(c128* a, c128* b, const double* __restrict__ G,
   }
 }
 
-// h = 1/2 (u + w) + v ys;  psi null: ynew = h;  else ynew = psi - i coef h (also to snap when given)
+// h = 1/2 (u + w) + sum_b V_ab ys_b over the [B ns] planes of npts points (plane f / npts = m ns + a; v null: no
+// potential);  psi null: ynew = h;  else ynew = psi - i coef h (also to snap when given).  ynew may be ys for ns = 1
+// alone.
 __global__ void wpg_combine_kernel(const c128* u, const c128* w, const c128* ys, const c128* psi, const c128* v,
-                                   long n, long npts, double coef, c128* ynew, c128* snap, size_t sstride) {
+                                   long n, long npts, int ns, double coef, c128* ynew, c128* snap, size_t sstride) {
   for (long f = blockIdx.x * (long)blockDim.x + threadIdx.x; f < n; f += (long)gridDim.x * blockDim.x) {
-    const long m = f / npts, p = f - m * npts;
-    const c128 yv = ys[f];
-    const c128 h = cadd(cscale(cadd(u[f], w[f]), 0.5), cmul(v ? v[p] : cmk(0, 0), yv));
+    const long mp = f / npts, p = f - mp * npts;
+    const int sa = (int)(mp % ns);
+    c128 vy = cmk(0, 0);
+    if (v) {
+      const c128* yb = ys + (size_t)(mp - sa) * npts + p;
+      const c128* vb = v + (size_t)sa * ns * npts + p;
+      vy = wpg_vy_any(vb[0], yb[0]);
+      for (int b = 1; b < ns; ++b) vy = cadd(vy, wpg_vy_any(vb[(size_t)b * npts], yb[(size_t)b * npts]));
+    }
+    const c128 h = cadd(cscale(cadd(u[f], w[f]), 0.5), vy);
     if (!psi) {
       ynew[f] = h;
       continue;
     }
     const c128 yn = cadd(psi[f], cscale(cmulmi(h), coef));
     ynew[f] = yn;
-    if (snap) snap[(size_t)m * sstride + p] = yn;
+    if (snap) snap[(size_t)(mp / ns) * sstride + (size_t)sa * npts + p] = yn;
   }
 }
 

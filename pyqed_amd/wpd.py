@@ -7,7 +7,8 @@ Every propagation step runs in libqdyn (qd_spo1d_run / qd_spo2_run_ex / qd_spo3_
 Populations, mean positions and the electronic reduced density matrix are reduced on the device
 (qd_spo_observe), after the run from states or inside it (run(..., observe=...), qd_spo*_run_observed).
 Curvilinear coordinates (wpd.py:1783-1940: adiabatic_2d, KEO, PEO, hpsi) apply the G-matrix kinetic operator and run
-its RK4 steps in libqdyn (qd_wp2_gmat_apply / qd_wp2_gmat_rk4).
+its RK4 steps in libqdyn (qd_wp2_gmat_apply / qd_wp2_gmat_rk4); on coupled surfaces (a potential [nx, ny, ns, ns];
+SPO2(coords='curvilinear', G=G)) qd_wp2_gmat_ms_apply / qd_wp2_gmat_ms_rk4.
 """
 from __future__ import annotations
 
@@ -382,7 +383,12 @@ class _PointPropagators:
 
 
 class SPO2(_PointPropagators):
-    """Drop-in for pyqed.wpd.SPO2 (wpd.py:379-887), linear and Jacobi coordinates."""
+    """Drop-in for pyqed.wpd.SPO2 (wpd.py:379-887), linear and Jacobi coordinates.
+
+    coords='curvilinear' with a metric G [nx, ny, 2, 2] (extension: the reference's constructor takes both and its
+    header says "for curvilinear coordinates, use RK4 method", but its run dies on an unbound KEO): no split operator
+    exists for K = 1/2 sum p_r G_rs(x, y) p_s, so run / run_batch take RK4 steps of
+    i dpsi_a/dt = K psi_a + sum_b v_ab psi_b (curvilinear_run, qd_wp2_gmat_ms_rk4) with the same results interface."""
 
     def __init__(self, x, y, mass=None, nstates=2, coords='linear', G=None, abc=False):
         self.x = x
@@ -468,6 +474,11 @@ class SPO2(_PointPropagators):
         nx, ny = self.nx, self.ny
         self.kx = 2. * np.pi * fftfreq(nx, interval(self.x))
         self.ky = 2. * np.pi * fftfreq(ny, interval(self.y))
+        if self.coords == 'curvilinear':   # RK4 on the G-matrix operator: no exp_K, no exp_V
+            _gmat_check_G(self.G, nx, ny, f"the grid {(nx, ny)}")
+            self._d2a = self._apes = self._d2a_dev = None
+            self._eig_pending = self.v is not None   # d2a for observe='adiabatic': host eigh on first access
+            return
         self._build_keo(dt)
         if self.v is None:
             raise ValueError('The diabatic PES is not specified.')
@@ -565,6 +576,50 @@ class SPO2(_PointPropagators):
         r._recorded = (r.population, r.xAve[0], r.xAve[1])
         return r
 
+    def _curvilinear_states(self, psi0s, dt, nt, nout):
+        """curvilinear_run of psi0s [B, nx, ny, ns] on self.v and self.G: device tensors (psi, snap)."""
+        if self.v is None:
+            raise ValueError('The diabatic PES is not specified.')
+        shape = tuple(psi0s.shape) if isinstance(psi0s, torch.Tensor) else np.shape(psi0s)
+        if shape[1:] != (self.nx, self.ny, self.ns):
+            raise ValueError(f"psi0s must be [B, {self.nx}, {self.ny}, {self.ns}]; got {shape}")
+        return curvilinear_run(self.x, self.y, psi0s, self.v, self.G, dt, nt, nout)
+
+    def _observe_snapshots(self, snap, basis):
+        """rdm [B, nsnap, ns, ns] and mom [B, nsnap, 2, ns] of recorded states snap [B, nsnap, nx, ny, ns]
+        (qd_spo_observe, after the run)."""
+        B, nsnap, ns = int(snap.shape[0]), int(snap.shape[1]), self.ns
+        if B * nsnap == 0:
+            return (torch.zeros((B, nsnap, ns, ns), dtype=torch.complex128, device=snap.device),
+                    torch.zeros((B, nsnap, 2, ns), dtype=torch.float64, device=snap.device))
+        rdm, mom = observe_states(snap.reshape((B * nsnap,) + tuple(snap.shape[2:])), self._axes(), basis=basis)
+        return rdm.reshape(B, nsnap, ns, ns), mom.reshape(B, nsnap, 2, ns)
+
+    def _run_curvilinear(self, psi0, dt, nt, t0, nout, return_states, observe):
+        """run on curvilinear coordinates: RK4 steps, the observables reduced from the recorded states after the run.
+        The snapshots [nt // nout, nx, ny, ns] (16 (nt // nout) nx ny ns bytes) stay on the device until they are
+        reduced, also with return_states=False, which only spares their copy to the host."""
+        psi, snap = self._curvilinear_states(np.asarray(psi0)[None], dt, nt, nout)
+        r = ResultSPO2(dt=dt, psi0=psi0, Nt=nt, t0=t0, nout=nout)
+        r.x = self.x
+        r.y = self.y
+        r.psilist = [psi0]
+        if return_states:
+            host = snap[0].cpu().numpy()
+            r.psilist += [host[k] for k in range(host.shape[0])]
+        r.psi = psi[0].cpu().numpy()
+        if observe is not None:
+            basis = self._obs_basis(observe, psi.device)
+            rdm0, mom0 = self._first_row(psi0, basis, psi.device)
+            rdm, mom = self._observe_snapshots(snap, basis)
+            rdm = torch.cat([rdm0, rdm[0]]).cpu().numpy()
+            mom = torch.cat([mom0, mom[0]]).cpu().numpy()
+            r.rdm = rdm
+            r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
+            r.xAve = [mom[:, 0].sum(axis=-1), mom[:, 1].sum(axis=-1)]
+            r._recorded = (r.population, r.xAve[0], r.xAve[1])
+        return r
+
     def run_batch(self, psi0s, dt=0.01, nt=1, nout=1, device=None, observe=None, keep_states=True):
         """Extension: B independent wavepackets psi0s [B, nx, ny, ns] on one potential, Strang steps as
         run(return_states=True) for each (qd_spo2_run_batch: one launch per pass for the whole batch).
@@ -575,8 +630,19 @@ class SPO2(_PointPropagators):
         inside the run (qd_spo2_run_observed) and returns (psi, snap or None, obs): obs is a dict of device tensors,
         rdm [B, nt//nout, ns, ns], mom [B, nt//nout, 2, ns] (mom[b, k, d, a] = <x_d> on state a) and population
         [B, nt//nout, ns], for the recorded states only (no psi0 row).  keep_states=False keeps no snapshots: the
-        run then holds one scratch state per member instead of nt//nout."""
+        run then holds one scratch state per member instead of nt//nout.
+
+        Curvilinear coordinates: curvilinear_run with self.v and self.G (RK4 steps; a device tensor psi0s stays on its
+        device, `device` is not consulted), the same returns; observe reduces the recorded states after the run, so the
+        snapshots are on the device until then whatever keep_states says."""
         self.build(dt=dt)
+        if self.coords == 'curvilinear':
+            psi, snap = self._curvilinear_states(psi0s, dt, nt, nout)
+            if observe is None:
+                return psi, snap
+            rdm, mom = self._observe_snapshots(snap, self._obs_basis(observe, psi.device))
+            return psi, (snap if keep_states else None), \
+                {"rdm": rdm, "mom": mom, "population": torch.diagonal(rdm, dim1=-2, dim2=-1).real}
         dev = device or default_device()
         _lib.ensure_device(dev)
         psi = psi0s if isinstance(psi0s, torch.Tensor) else _dev_c128(psi0s, dev)
@@ -622,8 +688,13 @@ class SPO2(_PointPropagators):
         reduced on the device inside the run (qd_spo2_run_observed): r.population [nt//nout + 1, ns], r.rdm
         [nt//nout + 1, ns, ns], r.xAve = [xAve, yAve] (summed over states, as position()).  return_states=True keeps
         the states too; return_states=False keeps none -- psilist == [psi0], one state of device scratch instead of
-        nt//nout, Strang not merged arithmetic -- and get_population() / position() return the recorded arrays."""
+        nt//nout, Strang not merged arithmetic -- and get_population() / position() return the recorded arrays.
+
+        coords='curvilinear' (extension): nt//nout*nout RK4 steps of the G-matrix operator in place of Strang steps,
+        the same psilist, r.psi and observe results (_run_curvilinear: observables reduced after the run)."""
         self.build(dt=dt)
+        if self.coords == 'curvilinear':
+            return self._run_curvilinear(psi0, dt, nt, t0, nout, return_states, observe)
         if observe is not None:
             return self._run_observed(psi0, dt, nt, t0, nout, return_states, observe)
         psi, states = self._propagate(psi0, dt, nt, nout, merged=not return_states)
@@ -651,6 +722,10 @@ class SPO2NH(SPO2):
         the GPU (qd_spo_expm, scaling and squaring, no eigenvectors) for ns <= 1024.  The right eigenvectors and their
         overlap (right_eigenstates, ovlp_rr; nonherm.eig order, eigenvalues by argsort) are host eig results made
         on first access (position() reads ovlp_rr)."""
+        if self.coords == 'curvilinear':
+            raise NotImplementedError("SPO2NH with coords='curvilinear': the non-Hermitian class is not covered; "
+                                      "SPO2(coords='curvilinear', G=G) propagates a complex potential (RK4 assumes no "
+                                      "Hermiticity), without SPO2NH's right-eigenvector observables")
         nx, ny = self.nx, self.ny
         self.kx = 2. * np.pi * fftfreq(nx, interval(self.x))
         self.ky = 2. * np.pi * fftfreq(ny, interval(self.y))
@@ -805,6 +880,9 @@ class SPO3(_PointPropagators):
         if self.coords == 'jacobi':
             raise NotImplementedError("SPO3 with coords='jacobi': the reference's _KEO_jacobi (wpd.py:1434-1469) is the "
                                       "2-D SPO2 operator applied to a 3-D grid and fails there; no 3-D Jacobi KEO exists")
+        if self.coords == 'curvilinear':
+            raise NotImplementedError("SPO3 with coords='curvilinear': a 3-D metric G [nx, ny, nz, 3, 3] is not "
+                                      "covered; the G-matrix propagator is two-dimensional (SPO2)")
         if self.coords != 'linear':
             raise ValueError(f"unknown coordinates {self.coords!r}")
         self.kx = 2. * np.pi * fftfreq(self.nx, self.dx)
@@ -914,13 +992,7 @@ def _gmat_check(psi, G, v, nkx, nky):
     if len(shape) not in (2, 3):
         raise ValueError(f"psi must be [nx, ny] or a batch [B, nx, ny]; got {shape}")
     nx, ny = int(shape[-2]), int(shape[-1])
-    if G is None:
-        raise ValueError("curvilinear coordinates need the metric G [nx, ny, 2, 2]")
-    gshape = tuple(G.shape) if isinstance(G, torch.Tensor) else np.shape(G)
-    if gshape != (nx, ny, 2, 2):
-        raise ValueError(f"G must be {(nx, ny, 2, 2)} for psi {shape}; got {gshape}")
-    if _is_complex_nonzero(G):
-        raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
+    _gmat_check_G(G, nx, ny, f"psi {shape}")
     if v is not None:
         vshape = tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)
         if vshape != (nx, ny):
@@ -928,6 +1000,50 @@ def _gmat_check(psi, G, v, nkx, nky):
     if (nkx, nky) != (nx, ny):
         raise ValueError(f"kx, ky have lengths {(nkx, nky)}; psi {shape} needs {(nx, ny)}")
     return nx, ny, len(shape) == 3
+
+
+def _gmat_check_G(G, nx, ny, what):
+    if G is None:
+        raise ValueError("curvilinear coordinates need the metric G [nx, ny, 2, 2]")
+    gshape = tuple(G.shape) if isinstance(G, torch.Tensor) else np.shape(G)
+    if gshape != (nx, ny, 2, 2):
+        raise ValueError(f"G must be {(nx, ny, 2, 2)} for {what}; got {gshape}")
+    if _is_complex_nonzero(G):
+        raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
+
+
+def _is_ms(v):
+    """A 4-D potential [nx, ny, ns, ns] selects the coupled-surface operator."""
+    return v is not None and len(tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)) == 4
+
+
+def _gmat_check_ms(psi, G, v, nkx, nky):
+    """_gmat_check for coupled surfaces: v [nx, ny, ns, ns], psi [nx, ny, ns] or a batch [B, nx, ny, ns].  Returns
+    (nx, ny, ns, batched)."""
+    shape = tuple(psi.shape) if isinstance(psi, torch.Tensor) else np.shape(psi)
+    vshape = tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)
+    want = "v [nx, ny, ns, ns] needs psi [nx, ny, ns] or a batch [B, nx, ny, ns]"
+    if len(shape) not in (3, 4):
+        raise ValueError(f"{want}; got psi {shape}")
+    nx, ny, ns = int(shape[-3]), int(shape[-2]), int(vshape[-1])
+    if vshape != (nx, ny, ns, ns) or ns < 1:
+        raise ValueError(f"v must be [nx, ny, ns, ns] = {(nx, ny)} + (ns, ns) for psi {shape}; got {vshape}")
+    if int(shape[-1]) != ns:
+        raise ValueError(f"{want}: v {vshape} has ns = {ns}; got psi {shape}")
+    _gmat_check_G(G, nx, ny, f"psi {shape}")
+    if (nkx, nky) != (nx, ny):
+        raise ValueError(f"kx, ky have lengths {(nkx, nky)}; psi {shape} needs {(nx, ny)}")
+    return nx, ny, ns, len(shape) == 4
+
+
+def _gmat_dev_ms(psi, G, v, kx, ky):
+    """_gmat_dev for coupled surfaces, in the kernels' plane layout: psi [B, ns, nx, ny] (always a copy) and
+    V [ns, ns, nx, ny], permuted on the device."""
+    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi, G, v, kx, ky)
+    if t.dim() == 3:
+        t = t[None]
+    planes = t.permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format)   # contiguous() copies nothing at ns = 1
+    return dev, planes, Gd, vd.permute(2, 3, 0, 1).contiguous(), kxd, kyd
 
 
 def _gmat_dev(psi, G, v, kx, ky):
@@ -952,7 +1068,19 @@ def _gmat_dev(psi, G, v, kx, ky):
 
 
 def _gmat_apply(psi, kx, ky, v, G):
-    """(K + v) psi on the device (qd_wp2_gmat_apply); returns a device tensor shaped like psi."""
+    """(K + v) psi on the device (qd_wp2_gmat_apply, or qd_wp2_gmat_ms_apply for v [nx, ny, ns, ns]); returns a device
+    tensor shaped like psi."""
+    if _is_ms(v):
+        nx, ny, ns, batched = _gmat_check_ms(psi, G, v, len(kx), len(ky))
+        dev, t, Gd, vd, kxd, kyd = _gmat_dev_ms(psi, G, v, kx, ky)
+        out = torch.empty_like(t)
+        with torch.cuda.device(dev):
+            rc = _lib.load().qd_wp2_gmat_ms_apply(t.data_ptr(), int(t.shape[0]), ns, Gd.data_ptr(), vd.data_ptr(),
+                                                  kxd.data_ptr(), kyd.data_ptr(), nx, ny, out.data_ptr(),
+                                                  _lib.stream_ptr(dev))
+        _lib.check(rc, "qd_wp2_gmat_ms_apply")
+        out = out.permute(0, 2, 3, 1).contiguous()
+        return out if batched else out[0]
     nx, ny, batched = _gmat_check(psi, G, v, len(kx), len(ky))
     dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi, G, v, kx, ky)
     out = torch.empty_like(t)
@@ -982,7 +1110,9 @@ def PEO(psi, v):
 
 
 def hpsi(psi, kx, ky, v, G):
-    """wpd.py:1935-1940: -1j (K psi + v psi), one library call for K psi + v psi; v real or complex."""
+    """wpd.py:1935-1940: -1j (K psi + v psi), one library call for K psi + v psi; v real or complex.
+    Extension: v [nx, ny, ns, ns] (any complex matrix per point) with psi [nx, ny, ns] or [B, nx, ny, ns] is the
+    coupled-surface operator, -1j (K psi_a + sum_b v_ab psi_b)."""
     return _like_input(-1j * _gmat_apply(psi, kx, ky, v, G), psi)
 
 
@@ -990,9 +1120,26 @@ def curvilinear_run(x, y, psi0s, v, G, dt, nt, nout=1):
     """Extension: RK4 propagation of B wavepackets psi0s [B, nx, ny] (or one, [nx, ny]) in curvilinear coordinates on
     one potential and metric (qd_wp2_gmat_rk4, one launch per pass for the whole batch).  Runs (nt // nout) nout steps,
     as SPO2.run_batch; returns (final states [B, nx, ny], snapshots [B, nt // nout, nx, ny]) as device tensors,
-    whatever psi0s was (ndarray, host or device tensor).  psi0s is not modified."""
+    whatever psi0s was (ndarray, host or device tensor).  psi0s is not modified.
+
+    Coupled surfaces: v [nx, ny, ns, ns] with psi0s [B, nx, ny, ns] (or one, [nx, ny, ns]) integrates
+    i dpsi_a/dt = K psi_a + sum_b v_ab psi_b (qd_wp2_gmat_ms_rk4) and returns ([B, nx, ny, ns],
+    [B, nt // nout, nx, ny, ns]).  The kernels hold the states as planes; the permutes happen on the device."""
     if nout < 1 or nt < 0:
         raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
+    if _is_ms(v):
+        nx, ny, ns, _ = _gmat_check_ms(psi0s, G, v, len(x), len(y))
+        kx = 2. * np.pi * fftfreq(nx, interval(x)) if nx > 1 else np.zeros(1)
+        ky = 2. * np.pi * fftfreq(ny, interval(y)) if ny > 1 else np.zeros(1)
+        dev, psi, Gd, vd, kxd, kyd = _gmat_dev_ms(psi0s, G, v, kx, ky)
+        B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
+        snap = torch.empty((B, nsnap, ns, nx, ny), dtype=torch.complex128, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.load().qd_wp2_gmat_ms_rk4(psi.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(), kxd.data_ptr(),
+                                                kyd.data_ptr(), nx, ny, float(dt), nsnap * int(nout), int(nout),
+                                                snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
+        _lib.check(rc, "qd_wp2_gmat_ms_rk4")
+        return psi.permute(0, 2, 3, 1).contiguous(), snap.permute(0, 1, 3, 4, 2).contiguous()
     nx, ny, _ = _gmat_check(psi0s, G, v, len(x), len(y))
     kx = 2. * np.pi * fftfreq(nx, interval(x)) if nx > 1 else np.zeros(1)
     ky = 2. * np.pi * fftfreq(ny, interval(y)) if ny > 1 else np.zeros(1)
