@@ -624,6 +624,31 @@ int qd_wp2_gmat_ms_rk4(qd_c128* psi, int B, int ns, const double* G, const qd_c1
                        const double* ky, int nx, int ny, double dt, int nsteps, int nout, qd_c128* snap, void* stream);
 
 /*
+ * The same in three curvilinear coordinates (extension: the reference's SPO3 stores a metric and never reads it):
+ * K psi = 1/2 sum_rs p_r G_rs(x, y, z) p_s psi with a real 3 x 3 metric G [nx][ny][nz][3][3] float64 (all nine entries
+ * read, no symmetry assumed), D_a f = IFFT_a(k_a FFT_a f), phi_r = sum_s G_rs D_s y,
+ * H y = 1/2 (D_x phi_x + D_y phi_y + D_z phi_z) + v y, RK4 in Horner form.  psi, out [B][nx][ny][nz], v [nx][ny][nz]
+ * complex128 or NULL, kx [nx], ky [ny], kz [nz] float64, snap [B][nsteps/nout][nx][ny][nz] or NULL.  On ns coupled
+ * surfaces (the _ms calls) the states are planes: psi, out [B][ns][nx][ny][nz], V [ns][ns][nx][ny][nz] complex128 (no
+ * Hermiticity assumed) or NULL, snap [B][nsteps/nout][ns][nx][ny][nz]; the single-surface calls are the ns = 1 case of
+ * the same code.  Every axis a power of two in [16, 256]: fused passes with every transform on LDS, 16 launches per
+ * step behind two per call; every other shape (an axis of length 1 included): the any-length transforms.
+ * B ns nx ny nz < 2^31 and ns ns nx ny nz < 2^31; out must not alias psi; nsteps == 0: no-op; arguments are checked
+ * before any launch.  Asynchronous on `stream` and capturable; scratch from the arena (rk4 on the fused path: seven
+ * states for ns > 1, six for ns = 1).
+ */
+int qd_wp3_gmat_apply(const qd_c128* psi, int B, const double* G, const qd_c128* v, const double* kx,
+                      const double* ky, const double* kz, int nx, int ny, int nz, qd_c128* out, void* stream);
+int qd_wp3_gmat_rk4(qd_c128* psi, int B, const double* G, const qd_c128* v, const double* kx, const double* ky,
+                    const double* kz, int nx, int ny, int nz, double dt, int nsteps, int nout, qd_c128* snap,
+                    void* stream);
+int qd_wp3_gmat_ms_apply(const qd_c128* psi, int B, int ns, const double* G, const qd_c128* V, const double* kx,
+                         const double* ky, const double* kz, int nx, int ny, int nz, qd_c128* out, void* stream);
+int qd_wp3_gmat_ms_rk4(qd_c128* psi, int B, int ns, const double* G, const qd_c128* V, const double* kx,
+                       const double* ky, const double* kz, int nx, int ny, int nz, double dt, int nsteps, int nout,
+                       qd_c128* snap, void* stream);
+
+/*
  * RK4 with a dense Liouville-space generator, d v/dt = L v (B vectors).
  * Replaces the csr GEMV loop of pyqed/oqs.py:436-463 (_redfield + rhs) for any
  * dense superoperator.  L [N2][N2], v [B][N2] in/out (row-major vec(rho)),

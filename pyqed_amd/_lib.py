@@ -152,6 +152,14 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "qd_wp2_gmat_ms_rk4": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                    c_double, c_int, c_int, c_void_p, c_void_p]),
+    "qd_wp3_gmat_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_void_p, c_void_p]),
+    "qd_wp3_gmat_rk4": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                c_double, c_int, c_int, c_void_p, c_void_p]),
+    "qd_wp3_gmat_ms_apply": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_int, c_int, c_void_p, c_void_p]),
+    "qd_wp3_gmat_ms_rk4": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p]),
     "qd_superop_from_glf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "qd_superop_lindblad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "qd_superop_rk4": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p, c_int, c_void_p,

@@ -129,6 +129,7 @@ __global__ __launch_bounds__(C * L / 4) void wp2_gmat_col_kernel(const c128* y, 
 //   WPG_STAGE: ynew = psi - i coef (1/2 (u + D_y phy) + sum_b V_ab ys_b), also to snap when given; dy = D_y ynew
 // ynew may be psi (read at the thread's own plane and points only).  ynew may be ys for ns = 1 alone: a thread reads
 // the points it writes before it writes them, but the planes b != a of ys belong to other workgroups.
+// wp_gmat3.hip instantiates this kernel too, as its Z pass over nx ny rows of nz points: a change here changes its bits.
 enum WpgRowMode { WPG_PRO = 0, WPG_APPLY = 1, WPG_STAGE = 2 };
 
 template <int L, int MODE>

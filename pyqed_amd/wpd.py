@@ -8,7 +8,8 @@ Populations, mean positions and the electronic reduced density matrix are reduce
 (qd_spo_observe), after the run from states or inside it (run(..., observe=...), qd_spo*_run_observed).
 Curvilinear coordinates (wpd.py:1783-1940: adiabatic_2d, KEO, PEO, hpsi) apply the G-matrix kinetic operator and run
 its RK4 steps in libqdyn (qd_wp2_gmat_apply / qd_wp2_gmat_rk4); on coupled surfaces (a potential [nx, ny, ns, ns];
-SPO2(coords='curvilinear', G=G)) qd_wp2_gmat_ms_apply / qd_wp2_gmat_ms_rk4.
+SPO2(coords='curvilinear', G=G)) qd_wp2_gmat_ms_apply / qd_wp2_gmat_ms_rk4; in three coordinates (KEO3, hpsi3,
+curvilinear_run3, SPO3(coords='curvilinear', G=G) with G [nx, ny, nz, 3, 3]) the qd_wp3_gmat_* calls.
 """
 from __future__ import annotations
 
@@ -880,9 +881,17 @@ class SPO3(_PointPropagators):
         if self.coords == 'jacobi':
             raise NotImplementedError("SPO3 with coords='jacobi': the reference's _KEO_jacobi (wpd.py:1434-1469) is the "
                                       "2-D SPO2 operator applied to a 3-D grid and fails there; no 3-D Jacobi KEO exists")
-        if self.coords == 'curvilinear':
-            raise NotImplementedError("SPO3 with coords='curvilinear': a 3-D metric G [nx, ny, nz, 3, 3] is not "
-                                      "covered; the G-matrix propagator is two-dimensional (SPO2)")
+        if self.coords == 'curvilinear':   # RK4 on the 3 x 3 G-matrix operator: no exp_K, no exp_V
+            dims = (self.nx, self.ny, self.nz)
+            if self.G is not None and len(_shape_of(self.G)) == 4:
+                raise NotImplementedError("SPO3 with coords='curvilinear' needs a 3-D metric G [nx, ny, nz, 3, 3]; two "
+                                          "curvilinear coordinates with a rectilinear third (a four-dimensional G "
+                                          f"{_shape_of(self.G)}) are not built")
+            _gmat3_check_G(self.G, *dims, f"the grid {dims}")
+            self.kx, self.ky, self.kz = (_gmat_k(n, a) for n, a in zip(dims, self._axes()))
+            self._d2a = self._apes = self._d2a_dev = None
+            self._eig_pending = self.V is not None   # d2a for observe='adiabatic': host eigh on first access
+            return
         if self.coords != 'linear':
             raise ValueError(f"unknown coordinates {self.coords!r}")
         self.kx = 2. * np.pi * fftfreq(self.nx, self.dx)
@@ -914,8 +923,14 @@ class SPO3(_PointPropagators):
 
         observe (extension, as SPO2.run): r.population [nt//nout + 1, ns], r.rdm [nt//nout + 1, ns, ns] and
         r.xAve = [xAve, yAve, zAve] of psi0 (row 0) and of the state after every nout steps, reduced inside the run
-        (qd_spo3_run_observed); with return_states=False no states are kept (psilist == [])."""
+        (qd_spo3_run_observed); with return_states=False no states are kept (psilist == []).
+
+        coords='curvilinear' (extension): nt//nout*nout RK4 steps of the 3 x 3 G-matrix operator on self.V
+        (curvilinear_run3, qd_wp3_gmat_ms_rk4) with the same psilist, r.psi and observe results; the observables are
+        reduced from the recorded states after the run, as SPO2._run_curvilinear does."""
         self.build(dt=dt)
+        if self.coords == 'curvilinear':
+            return self._run_curvilinear(psi0, dt, nt, t0, nout, return_states, observe)
         dev = default_device()
         _lib.ensure_device(dev)
         nsteps = (nt // nout) * nout
@@ -968,6 +983,33 @@ class SPO3(_PointPropagators):
             r.psilist = [host[k] for k in range(nsnap)]
         r.psi = psi.cpu().numpy()
         if observed:
+            r.rdm = rdm
+            r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
+            r.xAve = [mom[:, d].sum(axis=-1) for d in range(3)]
+        return r
+
+    def _run_curvilinear(self, psi0, dt, nt, t0, nout, return_states, observe):
+        """run on curvilinear coordinates (build has checked G).  The snapshots [nt // nout, nx, ny, nz, ns] stay on the
+        device until they are reduced, also with return_states=False, which only spares their copy to the host."""
+        if self.V is None:
+            raise ValueError('The diabatic PES is not specified.')
+        shape = (self.nx, self.ny, self.nz, self.nstates)
+        if np.shape(psi0) != shape:
+            raise ValueError(f"psi0 must be {list(shape)}; got {np.shape(psi0)}")
+        psi, snap = curvilinear_run3(self.x, self.y, self.z, np.asarray(psi0)[None], self.V, self.G, dt, nt, nout)
+        observed = observe is not None
+        r = Result(dt=dt, psi0=psi0, Nt=nt, t0=t0, nout=nout)
+        if return_states or not observed:
+            host = snap[0].cpu().numpy()
+            r.psilist = [host[k] for k in range(host.shape[0])]
+        r.psi = psi[0].cpu().numpy()
+        if observed:
+            basis = self._obs_basis(observe, psi.device)
+            rdm, mom = self._first_row(psi0, basis, psi.device)
+            if snap.shape[1]:
+                rdm1, mom1 = observe_states(snap[0], self._axes(), basis=basis)
+                rdm, mom = torch.cat([rdm, rdm1]), torch.cat([mom, mom1])
+            rdm, mom = rdm.cpu().numpy(), mom.cpu().numpy()
             r.rdm = rdm
             r.population = np.ascontiguousarray(np.einsum('kaa->ka', rdm).real)
             r.xAve = [mom[:, d].sum(axis=-1) for d in range(3)]
@@ -1177,3 +1219,139 @@ def adiabatic_2d(x, y, psi0, v, dt, Nt=0, coords='linear', mass=None, G=None):
     _, _, batched = _gmat_check(psi0, G, v, len(x), len(y))
     psi, _ = curvilinear_run(x, y, psi0, v, G, dt, int(Nt), 1)
     return _like_input(psi if batched else psi[0], psi0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Three curvilinear coordinates (extension): the 3 x 3 G-matrix operator and its RK4 propagation
+
+def _shape_of(a):
+    return tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+
+
+def _gmat_k(n, axis):
+    """k = 2 pi fftfreq(n, d) of an axis of n points, zeros(1) for an axis of length 1."""
+    return 2. * np.pi * fftfreq(n, interval(axis)) if n > 1 else np.zeros(1)
+
+
+def _gmat3_check_G(G, nx, ny, nz, what):
+    if G is None:
+        raise ValueError("curvilinear coordinates need the metric G [nx, ny, nz, 3, 3]")
+    if _shape_of(G) != (nx, ny, nz, 3, 3):
+        raise ValueError(f"G must be {(nx, ny, nz, 3, 3)} for {what}; got {_shape_of(G)}")
+    if _is_complex_nonzero(G):
+        raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
+
+
+def _gmat3_check(psi, G, v, nk):
+    """Shape and type checks of a 3-D curvilinear call, before any device call for ndarray and host-tensor operands.
+    v [nx, ny, nz] (or None) takes psi [nx, ny, nz] or a batch [B, nx, ny, nz]; v [nx, ny, nz, ns, ns] takes
+    psi [nx, ny, nz, ns] or [B, nx, ny, nz, ns].  Returns (dims, ns, batched), ns = 0 on a single surface."""
+    shape = _shape_of(psi)
+    vshape = None if v is None else _shape_of(v)
+    if vshape is not None and len(vshape) == 5:
+        want = "v [nx, ny, nz, ns, ns] needs psi [nx, ny, nz, ns] or a batch [B, nx, ny, nz, ns]"
+        if len(shape) not in (4, 5):
+            raise ValueError(f"{want}; got psi {shape}")
+        dims, ns = tuple(int(n) for n in shape[-4:-1]), int(vshape[-1])
+        if vshape != dims + (ns, ns) or ns < 1:
+            raise ValueError(f"v must be [nx, ny, nz, ns, ns] = {dims} + (ns, ns) for psi {shape}; got {vshape}")
+        if int(shape[-1]) != ns:
+            raise ValueError(f"{want}: v {vshape} has ns = {ns}; got psi {shape}")
+        batched = len(shape) == 5
+    else:
+        if len(shape) not in (3, 4):
+            raise ValueError(f"psi must be [nx, ny, nz] or a batch [B, nx, ny, nz]; got {shape}")
+        dims, ns, batched = tuple(int(n) for n in shape[-3:]), 0, len(shape) == 4
+        if vshape is not None and vshape != dims:
+            raise ValueError(f"v must be {dims} (or [nx, ny, nz, ns, ns]) for psi {shape}; got {vshape}")
+    _gmat3_check_G(G, *dims, f"psi {shape}")
+    if tuple(nk) != dims:
+        raise ValueError(f"kx, ky, kz have lengths {tuple(nk)}; psi {shape} needs {dims}")
+    return dims, ns, batched
+
+
+def _gmat3_dev(psi, G, v, ks, ns):
+    """Device operands in the kernels' layout: psi [B, max(ns, 1), nx, ny, nz] (always a copy), G float64,
+    V [ns, ns, nx, ny, nz] or v [nx, ny, nz] complex128 or None, and the three k vectors float64."""
+    dev = psi.device if isinstance(psi, torch.Tensor) and psi.device.type == "cuda" else default_device()
+    _lib.ensure_device(dev)
+    t = psi.to(device=dev, dtype=torch.complex128) if isinstance(psi, torch.Tensor) else _dev_c128(psi, dev)
+    if t.dim() == (4 if ns else 3):
+        t = t[None]
+    t = t.permute(0, 4, 1, 2, 3) if ns else t[:, None]
+    t = t.clone(memory_format=torch.contiguous_format)
+    if isinstance(G, torch.Tensor):
+        Gd = (G.real if G.is_complex() else G).to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        Gd = _dev_f64(np.real(G), dev)
+    vd = None
+    if v is not None:
+        vd = v.to(device=dev, dtype=torch.complex128) if isinstance(v, torch.Tensor) else _dev_c128(v, dev)
+        vd = (vd.permute(3, 4, 0, 1, 2) if ns else vd).contiguous()
+    f64 = lambda k: k.to(device=dev, dtype=torch.float64).contiguous() if isinstance(k, torch.Tensor) \
+        else _dev_f64(k, dev)
+    return dev, t, Gd, vd, [f64(k) for k in ks]
+
+
+def _gmat3_apply(psi, ks, v, G):
+    """(K + v) psi on the device (qd_wp3_gmat_apply, or qd_wp3_gmat_ms_apply for v [nx, ny, nz, ns, ns]); returns a
+    device tensor shaped like psi."""
+    dims, ns, batched = _gmat3_check(psi, G, v, [len(k) for k in ks])
+    dev, t, Gd, vd, kd = _gmat3_dev(psi, G, v, ks, ns)
+    out = torch.empty_like(t)
+    B = int(t.shape[0])
+    with torch.cuda.device(dev):
+        if ns:
+            name = "qd_wp3_gmat_ms_apply"
+            rc = _lib.load().qd_wp3_gmat_ms_apply(t.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(),
+                                                  *(k.data_ptr() for k in kd), *dims, out.data_ptr(),
+                                                  _lib.stream_ptr(dev))
+        else:
+            name = "qd_wp3_gmat_apply"
+            rc = _lib.load().qd_wp3_gmat_apply(t.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd),
+                                               *(k.data_ptr() for k in kd), *dims, out.data_ptr(),
+                                               _lib.stream_ptr(dev))
+    _lib.check(rc, name)
+    out = out.permute(0, 2, 3, 4, 1).contiguous() if ns else out[:, 0]
+    return out if batched else out[0]
+
+
+def KEO3(psi, kx, ky, kz, G):
+    """Extension: K psi = 1/2 sum_rs p_r G_rs p_s psi in three curvilinear coordinates, p_a psi = IFFT_a(k_a FFT_a psi),
+    G [nx, ny, nz, 3, 3] real with all nine entries read.  psi [nx, ny, nz] or a batch [B, nx, ny, nz]; ndarray in
+    gives ndarray out, a tensor comes back on its own device, as KEO."""
+    return _like_input(_gmat3_apply(psi, (kx, ky, kz), None, G), psi)
+
+
+def hpsi3(psi, kx, ky, kz, v, G):
+    """Extension: -1j (K psi + v psi) with KEO3's K; v [nx, ny, nz] real or complex.  v [nx, ny, nz, ns, ns] with
+    psi [nx, ny, nz, ns] or [B, nx, ny, nz, ns] is the coupled-surface operator, -1j (K psi_a + sum_b v_ab psi_b)."""
+    return _like_input(-1j * _gmat3_apply(psi, (kx, ky, kz), v, G), psi)
+
+
+def curvilinear_run3(x, y, z, psi0s, v, G, dt, nt, nout=1):
+    """Extension: curvilinear_run in three coordinates (qd_wp3_gmat_rk4; v [nx, ny, nz, ns, ns]: qd_wp3_gmat_ms_rk4).
+    Runs (nt // nout) nout RK4 steps of B wavepackets psi0s [B, nx, ny, nz] (or one) on one potential and metric
+    G [nx, ny, nz, 3, 3]; returns (final states [B, nx, ny, nz], snapshots [B, nt // nout, nx, ny, nz]) as device
+    tensors, with a trailing state axis on coupled surfaces.  psi0s is not modified."""
+    if nout < 1 or nt < 0:
+        raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
+    dims, ns, _ = _gmat3_check(psi0s, G, v, (len(x), len(y), len(z)))
+    ks = [_gmat_k(n, a) for n, a in zip(dims, (x, y, z))]
+    dev, psi, Gd, vd, kd = _gmat3_dev(psi0s, G, v, ks, ns)
+    B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
+    snap = torch.empty((B, nsnap, max(ns, 1)) + dims, dtype=torch.complex128, device=dev)
+    tail = (float(dt), nsnap * int(nout), int(nout), snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
+    with torch.cuda.device(dev):
+        if ns:
+            name = "qd_wp3_gmat_ms_rk4"
+            rc = _lib.load().qd_wp3_gmat_ms_rk4(psi.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(),
+                                                *(k.data_ptr() for k in kd), *dims, *tail)
+        else:
+            name = "qd_wp3_gmat_rk4"
+            rc = _lib.load().qd_wp3_gmat_rk4(psi.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd),
+                                             *(k.data_ptr() for k in kd), *dims, *tail)
+    _lib.check(rc, name)
+    if ns:
+        return psi.permute(0, 2, 3, 4, 1).contiguous(), snap.permute(0, 1, 3, 4, 5, 2).contiguous()
+    return psi[:, 0], snap[:, :, 0]
