@@ -541,7 +541,8 @@ int qd_tdse_pair_corr(const qd_c128* H, const qd_c128* A, const qd_c128* Bop,
  * start time).  fvals is a HOST array [nblocks][nd] (f_d(t_k), complex).
  *   psi  [B][N] in/out; snap [B][nblocks][N] psi after each block, or NULL;
  *   E [ne][N][N], obs [B][nblocks+1][ne] = <psi|E_m|psi> at t0 and after
- *   each block, or NULL.   Any N, 0 <= nd <= 16, nout >= 1.
+ *   each block, or NULL.   Any N, 0 <= nd <= 16, nout >= 1.  nblocks = 0
+ *   gives the t0 observables alone; Hd and fvals may be NULL then.
  */
 int qd_tdse_driven_rk4(const qd_c128* H0, const qd_c128* Hd, int nd,
                        const qd_c128* fvals, qd_c128* psi, int B, int N,

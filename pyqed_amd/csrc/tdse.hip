@@ -523,7 +523,8 @@ extern "C" int qd_tdse_driven_rk4(const qd_c128* H0, const qd_c128* Hd, int nd, 
                                   int B, int N, double dt, int nblocks, int nout, qd_c128* snap, const qd_c128* E,
                                   int ne, qd_c128* obs, void* stream) {
   WsScope wss_((hipStream_t)stream);  // call-scoped scratch (qd_runtime.hip)
-  QD_CHECK_ARG(H0 && psi && (nd == 0 || (Hd && fvals)), "qd_tdse_driven_rk4: null pointer");
+  // no block reads no drive: Hd and fvals (an empty [0][nd] array) may be null then
+  QD_CHECK_ARG(H0 && psi && (nd == 0 || nblocks == 0 || (Hd && fvals)), "qd_tdse_driven_rk4: null pointer");
   QD_CHECK_ARG(N >= 1 && B >= 1 && nblocks >= 0 && nout >= 1 && nd >= 0 && nd <= 16,
                "qd_tdse_driven_rk4: bad sizes N=%d B=%d nblocks=%d nout=%d nd=%d", N, B, nblocks, nout, nd);
   QD_CHECK_ARG(ne >= 0 && (ne == 0 || (E && obs)), "qd_tdse_driven_rk4: E/obs null but ne=%d", ne);

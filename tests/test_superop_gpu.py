@@ -39,7 +39,8 @@ def test_lindblad_superop_builder_matches_host_kron():
 def test_superop_rk4_matches_oracle(N, B, monkeypatch):
     """RK4 on vec(rho) with the device-built dense L vs the oracle's commutator-form RK4 (same linear ODE, same RK4:
     agreement to rounding).  B < 48: GEMV path (groups of <= 8 vectors); B >= 48: MFMA GEMM stages (N = 40 pads
-    N^2 = 1600 to 1664); N = 128 is the BASELINE config d1 size (L = 4 GiB)."""
+    N^2 = 1600 to 1664); N = 128 is the BASELINE config d1 size (L = 4 GiB).  Every member is compared on its own,
+    at N = 128 too: the oracle works on the N x N matrices, 64 of them take it 0.2 s."""
     import torch
     from oracle import lindblad as olb
     from pyqed_amd.oqs import lindblad_superop, superop_rk4
@@ -51,13 +52,14 @@ def test_superop_rk4_matches_oracle(N, B, monkeypatch):
     W = _t(np.eye(N, dtype=complex).reshape(1, N * N))  # vec(I^T): Tr(rho)
     obs, snap = superop_rk4(L, v, dt, steps, W, save_every=1)
     torch.cuda.synchronize()
-    sel = sorted({0, B // 2, B - 1})
-    ref = olb.lindblad_batch(H, cs, rho0[sel], dt, steps)
-    got = v.cpu().numpy().reshape(B, N, N)[sel]
+    ref = olb.lindblad_batch(H, cs, rho0, dt, steps)
+    got = v.cpu().numpy().reshape(B, N, N)
     assert relerr(got, ref) < TOL
+    assert max(relerr(got[b], ref[b]) for b in range(B)) < TOL
     assert np.allclose(obs.cpu().numpy()[:, :, 0], 1.0, atol=1e-12)  # trace kept at every step
     s = snap.cpu().numpy()
-    assert s.shape == (B, steps, N * N) and relerr(s[sel, -1].reshape(len(sel), N, N), ref) < TOL
+    assert s.shape == (B, steps, N * N) and relerr(s[:, -1].reshape(B, N, N), ref) < TOL
+    assert max(relerr(s[b, -1].reshape(N, N), ref[b]) for b in range(B)) < TOL
     del L
     torch.cuda.empty_cache()
 
@@ -65,7 +67,7 @@ def test_superop_rk4_matches_oracle(N, B, monkeypatch):
 @pytest.mark.parametrize("B,path", [(8, "superop_gemv"), (64, "superop_gemm")])
 def test_superop_gemm_and_gemv_paths_match_oracle(B, path):
     """Batches below 48 vectors run GEMV stages, from 48 the MFMA GEMM stages (qd_take_path): both against the
-    oracle's Lindblad RK4 (oqs.py:697-714) on a spread of members."""
+    oracle's Lindblad RK4 (oqs.py:697-714), every member on its own."""
     import torch
     from oracle import lindblad as olb
     from pyqed_amd.oqs import lindblad_superop, superop_rk4
@@ -79,9 +81,10 @@ def test_superop_gemm_and_gemv_paths_match_oracle(B, path):
     superop_rk4(L, v, 0.02, 4)
     hit, got = took(path)
     assert hit, got
-    sel = [0, B // 2, B - 1]
-    ref = olb.lindblad_batch(H, cs, rho0[sel], 0.02, 4)
-    assert relerr(v.cpu().numpy().reshape(B, N, N)[sel], ref) < TOL
+    ref = olb.lindblad_batch(H, cs, rho0, 0.02, 4)
+    out = v.cpu().numpy().reshape(B, N, N)
+    assert relerr(out, ref) < TOL
+    assert max(relerr(out[b], ref[b]) for b in range(B)) < TOL
 
 
 def test_redfield_superop_n128_matches_reference_tensor_and_evolution():

@@ -136,7 +136,8 @@ def test_tdse_row_and_gemm_paths_vs_oracle(N, B, save_every, path):
     """The row path (a wave per row and stage launch) and, where tdse.hip's dispatch takes it ((B >= 64 and N >= 512)
     or (B >= 128 and N >= 256)), the MFMA GEMM stages (padded [Bp][Np] state, split-K slabs): snapshots and
     observables (E_m = H, diag) against the oracle's RK4 (oracle.tdse restates mol.py:1603-1691); B = 64 / 130 and
-    N = 600 exercise the GEMM's padding to multiples of 128."""
+    N = 600 exercise the GEMM's padding to multiples of 128.  Every member's final state and snapshots and every
+    obs[b, idx, m] are compared."""
     import torch
     from oracle import tdse as otd
     from pyqed_amd.mol import tdse_rk4
@@ -157,12 +158,23 @@ def test_tdse_row_and_gemm_paths_vs_oracle(N, B, save_every, path):
     assert hit, got
     out = {"1": (psi.cpu().numpy(), snap.cpu().numpy(), obs.cpu().numpy())}
     psi, snap, obs = out["1"]
-    ref = psi0[0].copy()
+    ops = (H, Ed)
+
+    def expect(cols):   # <psi_b|E_m|psi_b> of the columns, [B, 2]
+        return np.stack([np.sum(np.conj(cols) * (e @ cols), axis=0) for e in ops], axis=1)
+
+    def check_obs(idx, cols):
+        e = expect(cols)
+        assert np.all(np.abs(obs[:, idx, :] - e) < 1e-12 * np.maximum(1, np.abs(e))), idx
+
+    assert snap.shape == (B, steps // save_every, N) and obs.shape == (B, steps // save_every + 1, 2)
+    ref = psi0.T.copy()   # every member: the oracle's step on the columns (the same arithmetic for each)
+    check_obs(0, ref)
     for s in range(steps):
         ref = otd._rk4(ref, H, dt)
         if (s + 1) % save_every == 0:
-            assert relerr(snap[0][(s + 1) // save_every - 1], ref) < 1e-12
-    assert relerr(psi[0], ref) < 1e-12
-    e0 = np.vdot(psi0[0], H @ psi0[0])
-    assert abs(obs[0, 0, 0] - e0) < 1e-12 * max(1, abs(e0))
+            idx = (s + 1) // save_every
+            assert max(relerr(snap[b][idx - 1], ref[:, b]) for b in range(B)) < 1e-12
+            check_obs(idx, ref)
+    assert max(relerr(psi[b], ref[:, b]) for b in range(B)) < 1e-12
     assert np.allclose(np.linalg.norm(psi, axis=1), 1, atol=1e-10)
