@@ -93,7 +93,9 @@ int qd_workspace_stats(size_t* reserved, size_t* used);
  *   QD_OPT_GLF_PATH     (QD_GLF_PATH, default QD_GLF_AUTO): the Lindblad / GLF
  *       batch path -- QD_GLF_SINGLE (single-trajectory launch, where it applies),
  *       QD_GLF_SPLIT (a workgroup per output block and phase; pair blocks for
- *       Hermitian batches), QD_GLF_PERSISTENT (a workgroup per matrix); for
+ *       Hermitian batches), QD_GLF_PERSISTENT (a workgroup per matrix),
+ *       QD_GLF_EIG (the caller of qd_lindblad_rk4_eig takes it at any batch
+ *       size; the other entry points dispatch by shape under it); for
  *       comparing the paths on one input;
  *   QD_OPT_IDLE_CAP_MIB (no environment variable, default -1 = 16384): the
  *       scratch arena's idle cache in MiB -- idle slabs beyond it are released once
@@ -109,6 +111,7 @@ int qd_workspace_stats(size_t* reserved, size_t* used);
 #define QD_GLF_SINGLE 1
 #define QD_GLF_SPLIT 2
 #define QD_GLF_PERSISTENT 3
+#define QD_GLF_EIG 4
 int qd_set_option(int opt, int value);
 int qd_get_option(int opt, int* value);      /* value: host pointer */
 int qd_take_path(char* buf, size_t len);     /* buf: host pointer   */
@@ -156,6 +159,35 @@ int qd_lindblad_rk4_herm(const qd_c128* H, const qd_c128* C, int nc,
                          qd_c128* rho, int B, int N, double dt, int nsteps,
                          const qd_c128* E, int ne, qd_c128* obs, qd_c128* snap,
                          int save_every, void* stream);
+
+/*
+ * The same propagation for EXACTLY Hermitian rho in the eigenbasis of
+ *     A = -iH - 1/2 sum_c C_c^+ C_c = V diag(lam) V^-1
+ * (the caller diagonalises A once per (H, C) on the host).  With
+ * rho~ = V^-1 rho V^-+ and C~_c = V^-1 C_c V,
+ *     d rho~/dt = Lam~ o rho~ + sum_c C~_c rho~ C~_c^+ ,  Lam~_ij = lam_i + conj(lam_j):
+ * the A term is an elementwise product and the dissipator, Hermitian on its own,
+ * is computed on and above the diagonal only.  The call transforms rho to rho~,
+ * runs nsteps Horner RK4 steps and transforms back; one workgroup per matrix.
+ *   lam   [128]            eigenvalues of A, zero beyond N
+ *   V, Vinv [128][128]     V and V^-1, identity block beyond N
+ *   Ct    [nc][128][128]   C~_c, zero beyond N
+ *   Et    [ne][128][128]   E~_m = V^+ E_m V, zero beyond N (Tr(E rho) = Tr(E~ rho~))
+ *   rho   [B][N][N], obs [B][nsteps+1][ne] as qd_lindblad_rk4; no snapshots
+ * Constraints: 64 < N <= 128, 1 <= nc <= 256.  The operands must stay valid
+ * until the stream has passed the call.  Stream-ordered; no host wait.
+ * Numerics: RK4 of a linear equation commutes with the fixed change of
+ * variables, so in exact arithmetic the result is qd_lindblad_rk4_herm's.  In
+ * floating point it differs from it in rounding, by a relative error of order
+ * cond_2(V)^2 * 1e-16 per basis change; the caller bounds cond_2(V) and the
+ * residual |V diag(lam) V^-1 - A| / |A| and keeps qd_lindblad_rk4_herm for
+ * operators that fail (a defective or nearly defective A).  The result is
+ * exactly Hermitian with an exactly real diagonal.
+ */
+int qd_lindblad_rk4_eig(const qd_c128* lam, const qd_c128* V,
+                        const qd_c128* Vinv, const qd_c128* Ct, int nc,
+                        qd_c128* rho, int B, int N, double dt, int nsteps,
+                        const qd_c128* Et, int ne, qd_c128* obs, void* stream);
 
 /*
  * Driven Lindblad RK4 (pyqed/oqs.py:1699-1806 _lindblad_driven):

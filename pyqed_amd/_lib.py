@@ -27,7 +27,7 @@ QD_OPT_COOP_LAUNCH = 0
 QD_OPT_FAKE_TIMEOUT = 1
 QD_OPT_GLF_PATH = 2
 QD_OPT_IDLE_CAP_MIB = 3
-GLF_PATHS = {"auto": 0, "single": 1, "split": 2, "persistent": 3}
+GLF_PATHS = {"auto": 0, "single": 1, "split": 2, "persistent": 3, "eig": 4}
 
 c_int = ctypes.c_int
 c_double = ctypes.c_double
@@ -52,6 +52,8 @@ SIGNATURES = {
                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "qd_lindblad_rk4_herm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_int,
                                      c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "qd_lindblad_rk4_eig": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double,
+                                    c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "qd_glf_rk4_herm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_int,
                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "qd_glf_rk4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double,
@@ -226,6 +228,13 @@ def set_option(opt: int, value: int) -> int:
     check(lib.qd_get_option(opt, ctypes.byref(prev)), "qd_get_option")
     check(lib.qd_set_option(opt, int(value)), "qd_set_option")
     return prev.value
+
+
+def get_option(opt: int) -> int:
+    """The current value of a process option (qd_get_option)."""
+    val = c_int(0)
+    check(load().qd_get_option(opt, ctypes.byref(val)), "qd_get_option")
+    return val.value
 
 
 def take_path() -> str:

@@ -1,4 +1,4 @@
-// cgemm_dma128.hpp — the Lindblad batch kernel's GEMM engine (glf_batch_kernel.hpp, its only user): 128-blocks staged
+// cgemm_dma128.hpp — the Lindblad batch kernels' GEMM engine (glf_batch_kernel.hpp, glf_eig_kernel.hpp): 128-blocks staged
 // by 16-byte global_load_lds (no staging registers, no ds_write pass), 3-product complex MACs.
 // An LDS-DMA load writes lane-linearly (wave base + lane * 16 B), so the A tile is [128 rows][16 k] without padding and
 // the k index is XOR-ed with row & 15 on the per-lane SOURCE address and again in the fragment read: the 16 lanes of one
@@ -256,6 +256,39 @@ __device__ __forceinline__ void cg_dma_herm_x_gemm(const CgSeg* segs, int nseg, 
   }
 #undef QD_HT
   cg_dma_finalise(acc);
+}
+
+// (P1, P2, P3) -> (re, im) on the tiles of mask M only (cg_dma_finalise on a wave's live tiles).
+template <unsigned M>
+__device__ __forceinline__ void cg_dma_finalise_live(CgAcc3& acc) {
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      if (!(M & (1u << (mi * 4 + nj)))) continue;
+      const d4 p1 = acc.re[mi][nj], p2 = acc.im[mi][nj];
+      acc.re[mi][nj] = p1 - p2;
+      acc.im[mi][nj] = (acc.p3[mi * 4 + nj] - p1) - p2;
+      asm volatile("" : "+v"(acc.re[mi][nj]), "+v"(acc.im[mi][nj]));
+    }
+}
+
+// The Hermitian sum D = sum_c B_c W_c on its own (no segment 0, no halving): wave W's part on the tiles on and above the
+// diagonal of the Hermitian tile layout, from a zeroed accumulator over every segment (segs[c] = (B_c, W_c), W_c in
+// full).  The tiles below the diagonal are never touched: with W fixed at compile time they take no registers, so a
+// wave holds at most 5 live tiles.  Called from a per-wave code path (switch on the wave index) by all threads; stages
+// its own tile 0 and ends with a workgroup barrier.  The caller makes the B_c complete and workgroup-visible first, and
+// finishes with cg_dma_finalise_live on the live tiles (after issuing whatever loads its epilogue wants in flight).
+template <int W>
+__device__ __forceinline__ void cg_dma_herm_d_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
+                                                   CgAcc3& acc) {
+  constexpr unsigned SK = cg_herm_mask(W, true);
+  cg_dma_zero(acc);
+  const int tps = K / CG_KT, T = nseg * tps;
+  const CgDmaStage st(segs, tps, lda, ldb);
+  st.issue(0, L, 0);
+  __syncthreads();
+  cg_dma_herm_x_range<W, SK>(0, T, T, st, L, acc);
 }
 
 }  // namespace qd

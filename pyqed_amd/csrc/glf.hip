@@ -586,7 +586,9 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   //  - else the persistent kernel (a workgroup per matrix).
   constexpr bool HSPLIT_Y64 = true;   // the Hermitian pair path's Y launch on 64-blocks (below)
   constexpr long SPLIT_MINWG = 512;   // workgroups per launch that a split-path block size must still give
-  const int force = option(QD_OPT_GLF_PATH);
+  // QD_GLF_EIG is taken by the caller of qd_lindblad_rk4_eig (glf_eig.hip); a call that arrives here under it is
+  // dispatched by its shape
+  const int force = option(QD_OPT_GLF_PATH) == QD_GLF_EIG ? QD_GLF_AUTO : option(QD_OPT_GLF_PATH);
   int split_bt = 0;
   bool hsplit = false;
   {
@@ -903,6 +905,24 @@ extern "C" int qd_glf_rk4_herm(const qd_c128* P, const qd_c128* L, const qd_c128
                  (const c128*)W, npairs, (c128*)rho, B, N, dt, nsteps, (const c128*)E, ne, (c128*)obs, (c128*)snap,
                  save_every, (hipStream_t)stream, nullptr, 0, nullptr, 1);
 }
+
+namespace qd {
+// zero-padded copy [B][N][N] -> [B][Np][Np] and back, for the other translation units of the GLF family (glf_eig.hip)
+int glf_pad(const c128* src, c128* dst, int B, int N, int Np, hipStream_t st) {
+  const size_t tot = (size_t)B * Np * Np;
+  hipLaunchKernelGGL(pad_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 65535)), dim3(256), 0, st, src, dst, B, N,
+                     Np);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+int glf_unpad(const c128* src, c128* dst, int B, int N, int Np, hipStream_t st) {
+  const size_t tot = (size_t)B * N * N;
+  hipLaunchKernelGGL(unpad_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 65535)), dim3(256), 0, st, src, dst, B,
+                     N, Np);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+}  // namespace qd
 
 namespace {
 // shared driver: A[b] <- Vl A[b] Vr for b < B; mode 0/1 = V^+ . V / V . V^+, mode 2 = L . R

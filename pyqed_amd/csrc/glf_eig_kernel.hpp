@@ -1,0 +1,230 @@
+// glf_eig_kernel.hpp — lindblad_eig_kernel: the Lindblad batch at Np = 128 propagated in the eigenbasis of the
+// effective Hamiltonian's generator A = -iH - 1/2 sum_c C_c^+ C_c = V Lam V^-1 (host plan: pyqed_amd/oqs.py).  With
+// rho~ = V^-1 rho V^-+ and C~_c = V^-1 C_c V the equation of motion is
+//     d rho~/dt = Lam~ o rho~ + sum_c C~_c rho~ C~_c^+ ,   Lam~_ij = lam_i + conj(lam_j)
+// so the A term is an elementwise multiply in the stage epilogue and only the dissipator is a GEMM.  The dissipator
+// of a Hermitian rho~ is Hermitian on its own: the second GEMM runs on the 36 16 x 16 tiles on and above the diagonal
+// (cg_dma_herm_d_gemm), each upper element's owner writes its mirror as the conjugate, and no X + X^+ pass through
+// LDS exists.  Per stage (64 + 36) nc tile-GEMMs for the 64 + (64 + 36) nc of glf_batch_kernel.hpp (nc = 1: 9,600
+// against 15,744 3-product MFMAs).  One persistent workgroup per matrix.  Only glf_eig.hip includes this header: next
+// to the kernels of glf.hip it changed the batch kernel's register allocation (3 spilled VGPRs).
+// One routine serves the two basis changes and the stages:
+//     rn = a base + hc (g Lam~ o r + sum_c (M_c r) W_c)
+// with a = g = 0, hc = 1 for a basis change (M = V^-1, W = V^-+ and M = V, W = V^+; the multiplications by zero are
+// exact on finite data) and a = g = 1, hc the Horner coefficient of the stage (glf_horner_coef) otherwise.
+// Every result is exactly Hermitian with an exactly real diagonal by construction.  RK4 of a linear equation commutes
+// with the fixed change of variables, so in exact arithmetic the back-transformed state is the persistent kernel's;
+// in floating point it differs from it in rounding, scaled by cond(V) (guarded on the host).
+// Register budget: the second GEMM holds at most 5 live tiles (120 accumulator VGPRs); 0 spilled VGPRs, 0 B scratch
+// (tools/isa_diff.py).
+#pragma once
+#include "cgemm_dma128.hpp"
+#include "glf_kernel.hpp"
+
+namespace qd {
+
+struct LindbladEigParams {
+  const c128* Ct;    // [nc][128][128]  C~_c
+  const c128* Ctd;   // [nc][128][128]  C~_c^+
+  const c128* V;     // [128][128]      V (identity on the padding), Vd = V^+, Vi = V^-1, Vid = V^-+
+  const c128* Vd;
+  const c128* Vi;
+  const c128* Vid;
+  const c128* lam;   // [128]           eigenvalues of A (zero on the padding)
+  const c128* eT;    // [ne][128][128]  (V^+ E_m V)^T
+  c128* rho;         // [B][128][128]   state (in/out, original basis)
+  c128* ws;          // [B][1 + nc][128][128]  stage buffer, Y_c
+  c128* obs;         // [B][nsteps+1][ne]
+  int nc, ne, nsteps;
+  double dt;
+  unsigned long long* tbuf;  // [B][8] per-phase ticks (QD_PHASE_TIMING diagnostics) or null
+};
+
+namespace {
+
+constexpr int EIG_NP = 128;
+
+// A double every lane holds alike, moved to scalar registers.
+__device__ __forceinline__ double eig_uniform(double v) {
+  const unsigned long long u = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+
+// m on the elements of wave W's tiles on and above the diagonal, in MFMA layout (q[mi * 4 + nj][e]; diagonal tiles load
+// all 256 elements, the values below the diagonal are discarded).  Every address is the matrix's base (scalar
+// registers) plus a 32-bit byte offset, the lane's own plus a uniform one.
+template <int W>
+__device__ __forceinline__ void eig_tile_loads(const c128* m, int lane, c128 (&q)[8][4]) {
+  const unsigned vu = (unsigned)((lane >> 4) * EIG_NP + (lane & 15)) * (unsigned)sizeof(c128);
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);
+      if (R > C) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned su = (unsigned)((16 * R + 4 * e) * EIG_NP) * (unsigned)sizeof(c128);   // uniform
+        q[mi * 4 + nj][e] = *reinterpret_cast<const c128*>(reinterpret_cast<const char*>(m + 16 * C) + (vu + su));
+      }
+    }
+}
+
+// Behind the second GEMM: wave W, on its tiles with R <= C, forms k_ij = D_ij + g Lam~_ij r_ij and rn_ij = a base_ij +
+// hc k_ij and writes rn_ji as the conjugate.  Diagonal tiles use ra <= lc only; on the diagonal Lam~_ii and r_ii are
+// real, so the accumulator's imaginary part is dropped and rn_ii is real.  Each upper element is read (r, base) and
+// written by one thread, loads first, so rn may be r or base.  The loads of r are issued behind the (P1, P2, P3) ->
+// (re, im) arithmetic and those of base once r is consumed: either set of five tiles next to all three accumulator
+// sets, or both next to two, spilled.
+template <int W>
+__device__ __forceinline__ void eig_tail(CgAcc3& A, const c128* r, const c128* base, c128* rn, const c128* lamS,
+                                         int lane, double a, double g, double hc) {
+  constexpr unsigned LIVE = 0xffu & ~cg_herm_mask(W, true);
+  const int lr = lane >> 4, lc = lane & 15;
+  const unsigned vu = (unsigned)(lr * EIG_NP + lc) * (unsigned)sizeof(c128);
+  const unsigned vm = (unsigned)(lc * EIG_NP + lr) * (unsigned)sizeof(c128);
+  c128 q[8][4];
+  cg_dma_finalise_live<LIVE>(A);
+  cg_sched_fence();   // the loads of r go into the registers the third accumulator set has left
+  eig_tile_loads<W>(r, lane, q);
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);
+      if (R > C) continue;
+      const c128 lj = lamS[16 * C + lc];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const c128 li = lamS[16 * R + lr + 4 * e], x = q[mi * 4 + nj][e];
+        const double gre = g * (li.re + lj.re), gim = g * (li.im - lj.im);   // g (lam_i + conj(lam_j))
+        A.re[mi][nj][e] += gre * x.re - gim * x.im;
+        A.im[mi][nj][e] += gre * x.im + gim * x.re;
+      }
+      // pinned tile by tile, as in cg_dma_finalise: sunk to the stores, the sums kept r live next to base
+      asm volatile("" : "+v"(A.re[mi][nj]), "+v"(A.im[mi][nj]));
+    }
+  cg_sched_fence();   // the loads of base go into the registers r has left
+  eig_tile_loads<W>(base, lane, q);
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      const int R = mi == 0 ? (W >> 1) : 7 - (W >> 1), C = cg_herm_ctile(W, nj);
+      if (R > C) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ra = lr + 4 * e;
+        const c128 k = cmk(A.re[mi][nj][e], A.im[mi][nj][e]);
+        c128 v = cadd(cscale(q[mi * 4 + nj][e], a), cscale(k, hc));
+        if (R == C && ra == lc) v.im = 0.0;
+        const unsigned su = (unsigned)((16 * R + 4 * e) * EIG_NP) * (unsigned)sizeof(c128);   // uniform, as sm
+        const unsigned sm = (unsigned)(16 * C * EIG_NP) * (unsigned)sizeof(c128);
+        char* u = reinterpret_cast<char*>(rn + 16 * C) + (vu + su);
+        char* t = reinterpret_cast<char*>(rn + 16 * R + 4 * e) + (vm + sm);
+        if (R < C || ra <= lc) *reinterpret_cast<c128*>(u) = v;
+        if (R < C || ra < lc) *reinterpret_cast<c128*>(t) = cconj(v);
+      }
+    }
+}
+
+__global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p) {
+  constexpr int BT = EIG_NP, Np = EIG_NP;
+  constexpr size_t NN = (size_t)Np * Np;
+  __shared__ CgLds<BT> L;
+  __shared__ c128 sred[CG_WG / 64];
+  __shared__ CgSeg segs[MAX_NC];   // the second GEMM's segment table (Y_c, W_c)
+  __shared__ c128 lamS[Np];
+
+  const int b = blockIdx.x;
+  c128* rho = p.rho + (size_t)b * NN;
+  c128* ws = p.ws + (size_t)b * (1 + p.nc) * NN;
+  c128* Y = ws + NN;
+  c128* obs = p.obs ? p.obs + (size_t)b * (p.nsteps + 1) * p.ne : nullptr;
+  if (threadIdx.x < Np) lamS[threadIdx.x] = p.lam[threadIdx.x];
+  __syncthreads();
+
+  CgAcc3 A;
+  QD_TIMING_DECL
+#ifdef QD_PHASE_TIMING
+  unsigned long long txf = 0;   // the basis changes' ticks, charged to slot 5 instead of the stages' slots
+#endif
+
+  // Phase ph of the call: 0 the change to the eigenbasis, 1 .. 4 nsteps the Horner stages, then the change back.
+  const int nph = 4 * p.nsteps + 2;
+  for (int ph = 0; ph < nph; ++ph) {
+    const bool xf = ph == 0 || ph == nph - 1;
+    const int stage = (ph - 1) & 3;
+    // Horner stages (glf_horner_coef): rho~ -> s1 -> s2 -> s3 -> rho~, s_m in place in ws; a basis change in place
+    const c128* r = (xf || stage == 0) ? rho : ws;
+    c128* rn = (xf || stage == 3) ? rho : ws;
+    const c128* M = ph == 0 ? p.Vi : xf ? p.V : p.Ct;
+    const c128* Wm = ph == 0 ? p.Vid : xf ? p.Vd : p.Ctd;
+    int n = xf ? 1 : p.nc;
+    double dts = p.dt;
+    asm volatile("" : "+s"(dts), "+s"(n));   // per phase: no coefficient or flag register held across the K loops
+    const double hc = eig_uniform(xf ? 1.0 : glf_horner_coef(dts, stage)), ag = xf ? 0.0 : 1.0;
+#ifdef QD_PHASE_TIMING
+    unsigned long long tkeep[4] = {tacc[0], tacc[1], tacc[2], tacc[3]};
+#endif
+    // One K-tile stream over the first GEMMs Y_c = M_c r: each stages tile 0 of the next one under its last K-tile.
+    // The second GEMM reads every Y_c, so it starts behind the last Y store (drained, then a barrier: one CU,
+    // write-through L1) with a prologue of its own; the last Y GEMM's lookahead has no follower to serve and restages
+    // its own tile 0 into the free buffer, unused.  The segment table is written ahead of the Y GEMMs' barriers; its
+    // last reader in the phase before is separated from these writes by that phase's closing barrier.
+    int tid0 = threadIdx.x;
+    asm volatile("" : "+v"(tid0));
+    if (tid0 == 0)
+      for (int c = 0; c < n; ++c) {
+        segs[c].A = Y + (size_t)c * NN;
+        segs[c].B = Wm + (size_t)c * NN;
+      }
+    for (int c = 0; c < n; ++c) {
+      const c128* Mc = M + (size_t)c * NN;
+      cg_dma_block_gemm_stream(Mc, r, c + 1 < n ? Mc + NN : Mc, r, c == 0, Np, Np, Np, L, A);
+      QD_TMARK(0);
+      c128* Yc = Y + (size_t)c * NN;
+      cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
+      QD_TMARK(1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Y stores are complete
+    __syncthreads();
+    {
+      int tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));   // the per-element index math stays inside the phase
+      const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
+      auto tail = [&](auto wc) {
+        constexpr int W = decltype(wc)::value;
+        cg_dma_herm_d_gemm<W>(segs, n, Np, Np, Np, L, A);
+        QD_TMARK(2);
+        eig_tail<W>(A, r, rho, rn, lamS, lane, ag, ag, hc);
+      };
+#define QD_EW(w) \
+  case w: tail(std::integral_constant<int, w>{}); break;
+      switch (wave) { QD_EW(0) QD_EW(1) QD_EW(2) QD_EW(3) QD_EW(4) QD_EW(5) QD_EW(6) default: QD_EW(7) }
+#undef QD_EW
+    }
+    __syncthreads();   // rn complete for the next phase's GEMMs, whose LDS-DMA stays behind this phase's reads
+    QD_TMARK(3);
+#ifdef QD_PHASE_TIMING
+    if (xf)
+      for (int q = 0; q < 4; ++q) {
+        txf += tacc[q] - tkeep[q];
+        tacc[q] = tkeep[q];
+      }
+#endif
+    if ((ph == 0 || (!xf && stage == 3)) && p.ne > 0) {   // observables on rho~: t0 and the end of every step
+      wg_observables(rho, p.eT, p.ne, NN, obs + (size_t)(ph / 4) * p.ne, sred);
+      __syncthreads();
+      QD_TMARK(4);
+    }
+  }
+#ifdef QD_PHASE_TIMING
+  tacc[5] += txf;
+#endif
+  QD_TIMING_FLUSH
+}
+
+}  // namespace
+}  // namespace qd

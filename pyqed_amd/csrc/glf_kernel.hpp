@@ -397,6 +397,9 @@ __global__ __launch_bounds__(CG_WG) void lindblad_rk4_kernel(LindbladParams p) {
 namespace qd {
 // The CHUNK instantiations of lindblad_rk4_kernel (nc > MAX_NC), one workgroup per matrix (glf_chunk.hip).
 int glf_launch_chunk(const LindbladParams& p, int B, hipStream_t st);
+// Zero-padded copy [B][N][N] -> [B][Np][Np] and back (glf.hip).
+int glf_pad(const c128* src, c128* dst, int B, int N, int Np, hipStream_t st);
+int glf_unpad(const c128* src, c128* dst, int B, int N, int Np, hipStream_t st);
 // Few matrices as one persistent launch, a workgroup per 16 x 16 output tile (glf_single.hip).
 int glf_single_max_batch(int Np, int nc, int herm = 0);
 int glf_single_run(const c128* P, const c128* Q, const c128* Lop, const c128* Rop, int nc, const c128* eT, int ne,

@@ -59,6 +59,133 @@ def _is_hermitian_cached(H: torch.Tensor) -> bool:
     return res
 
 
+# --------------------------------------------------------------------------- eigenbasis plan (qd_lindblad_rk4_eig)
+# Hermitian Lindblad batches at 64 < N <= 128 from EIG_MIN_BATCH matrices on are propagated in the eigenbasis of
+# A = -iH - 1/2 sum_c C_c^+ C_c = V diag(lam) V^-1 (include/qdyn.h): the A term becomes an elementwise
+# product and a stage costs 100 instead of 164 tile-GEMMs.  A is diagonalised once per (H, c_ops) on the host.
+EIG_NP = 128            # the kernel's padded dimension
+EIG_MIN_BATCH = 208     # where the library picks the persistent kernel (glf.hip)
+EIG_MAX_NC = 256        # MAX_NC of the kernels' LDS segment tables
+EIG_MIN_STEPS = 2       # a call's two basis changes cost half a step: a 1-step call ties with the persistent kernel
+                        # (0.614 against 0.612 ms at B = 256), 2 steps 0.978 against 1.140 (profiles/r11/lindblad)
+# Guards.  A non-normal A has a non-unitary V, and every rounding error of the transformed propagation comes back
+# multiplied by cond_2(V)^2; at an exceptional point A is defective and V singular.  EIG_MAX_COND is the largest
+# cond_2(V) of the damping sweep of tests/test_lindblad_eig_plan_cpu.py (gamma -> 4g in the two-level family embedded
+# in N = 65) at which the transformed-basis RK4 stays within 1e-12 of the oracle, 100 times inside the project's 1e-10:
+# cond 141 -> 3.5e-14, 447 -> 8.4e-13, 1.4e3 -> 2.6e-12; rounded down.  The synthetic operators of the benchmark sit at
+# 1.6, with the collapse operator times 20 at 95.  EIG_MAX_RESID bounds |V diag(lam) V^-1 - A|_F / |A|_F, a relative
+# error of the generator itself, at the same 1e-12 (accepted plans of the sweep: <= 6e-14).
+EIG_MAX_COND = 400.0
+EIG_MAX_RESID = 1e-12
+
+
+class EigPlan:
+    """Host part of the plan: lam [128], V, Vinv [128,128] (identity block on the padding), Ct [nc,128,128] = V^-1 C V
+    (zero on the padding), cond_2(V), the residual, and ok / reason from the guards."""
+
+    def __init__(self, H, cs):
+        import time
+        t0 = time.perf_counter()
+        H = np.asarray(H, dtype=np.complex128)
+        cs = np.asarray(cs, dtype=np.complex128).reshape(-1, H.shape[0], H.shape[0])
+        N, Np = H.shape[0], EIG_NP
+        self.N, self.nc = N, len(cs)
+        A = -1j * H - 0.5 * sum(c.conj().T @ c for c in cs)
+        self.ok, self.reason, self.cond, self.resid = False, "", np.inf, np.inf
+        try:
+            lam, V = np.linalg.eig(A)
+            sv = np.linalg.svd(V, compute_uv=False)
+            self.cond = float(sv[0] / sv[-1]) if sv[-1] > 0 else np.inf
+            Vinv = np.linalg.inv(V)
+            self.resid = float(np.linalg.norm((V * lam) @ Vinv - A) / max(np.linalg.norm(A), 1e-300))
+        except np.linalg.LinAlgError as e:
+            self.reason = f"eig failed: {e}"
+            return
+        finally:
+            self.seconds = time.perf_counter() - t0
+        if not (np.isfinite(self.cond) and self.cond <= EIG_MAX_COND):
+            self.reason = f"cond_2(V) = {self.cond:.3g} > {EIG_MAX_COND:g}"
+            return
+        if not (np.isfinite(self.resid) and self.resid <= EIG_MAX_RESID):
+            self.reason = f"residual {self.resid:.3g} > {EIG_MAX_RESID:g}"
+            return
+        self._V = V
+        self.lam = np.zeros(Np, np.complex128)
+        self.lam[:N] = lam
+        self.V, self.Vinv = np.eye(Np, dtype=np.complex128), np.eye(Np, dtype=np.complex128)
+        self.V[:N, :N], self.Vinv[:N, :N] = V, Vinv
+        self.Ct = np.zeros((self.nc, Np, Np), np.complex128)
+        for c in range(self.nc):
+            self.Ct[c, :N, :N] = Vinv @ cs[c] @ V
+        self.ok = True
+        self.seconds = time.perf_counter() - t0
+
+    def e_tilde(self, E):
+        """E~_m = V^+ E_m V padded with zeros: Tr(E rho) = Tr(E~ rho~) for rho~ = V^-1 rho V^-+."""
+        E = np.asarray(E, dtype=np.complex128).reshape(-1, self.N, self.N)
+        out = np.zeros((len(E), EIG_NP, EIG_NP), np.complex128)
+        for m in range(len(E)):
+            out[m, :self.N, :self.N] = self._V.conj().T @ E[m] @ self._V
+        return out
+
+
+def build_eig_plan(H, cs) -> EigPlan:
+    """The plan of (H [N,N], cs [nc,N,N]) from host arrays; no GPU work."""
+    return EigPlan(H, cs)
+
+
+_EIG_PLANS = {}   # (id(H), id(c_ops)) -> _EigEntry; keyed and invalidated like _HERM_CHECKED
+
+
+class _EigEntry:
+    def __init__(self, H, c_ops):
+        import weakref
+        self.refs = tuple((weakref.ref(t), t._version, t.data_ptr()) for t in (H, c_ops))
+        self.plan = build_eig_plan(H.cpu().numpy(), c_ops.cpu().numpy())
+        self.eops = {}
+        if self.plan.ok:
+            p = self.plan
+            self.dev = tuple(torch.from_numpy(a).to(H.device) for a in (p.lam, p.V, p.Vinv, p.Ct))
+
+    def current(self, tensors):
+        return all(r[0]() is t and r[1] == t._version and r[2] == t.data_ptr() for r, t in zip(self.refs, tensors))
+
+    def e_ops(self, e_ops, build):
+        import weakref
+        hit = self.eops.get(id(e_ops))
+        if hit is not None and hit[0]() is e_ops and hit[1] == e_ops._version and hit[2] == e_ops.data_ptr():
+            return hit[3]
+        if not build:
+            return None
+        Et = torch.from_numpy(self.plan.e_tilde(e_ops.cpu().numpy())).to(e_ops.device)
+        if len(self.eops) > 8:
+            self.eops.clear()
+        self.eops[id(e_ops)] = (weakref.ref(e_ops), e_ops._version, e_ops.data_ptr(), Et)
+        return Et
+
+
+def _eig_plan_cached(H, c_ops, e_ops):
+    """(entry, Et) of an accepted plan, or None: the plan was refused by its guards (cached as refused), or the stream
+    is capturing and the plan (or E~) is not cached yet -- capture allows no host work."""
+    build = not torch.cuda.is_current_stream_capturing()
+    key = (id(H), id(c_ops))
+    ent = _EIG_PLANS.get(key)
+    if ent is None or not ent.current((H, c_ops)):
+        if not build:
+            return None
+        if len(_EIG_PLANS) > 64:
+            _EIG_PLANS.clear()
+        ent = _EIG_PLANS[key] = _EigEntry(H, c_ops)
+    if not ent.plan.ok:
+        return None
+    Et = None
+    if e_ops is not None:
+        Et = ent.e_ops(e_ops, build)
+        if Et is None:
+            return None
+    return ent, Et
+
+
 def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor, dt: float, nsteps: int,
                  e_ops: torch.Tensor | None = None, save_every: int = 0, stream=None,
                  hermitian: bool | None = None):
@@ -78,6 +205,14 @@ def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor,
     the general kernel's split path, which spreads each matrix over many workgroups (qd_lindblad_rk4:
     8.3k instead of 1.3k steps/s for one N = 128 trajectory).  The Lindblad generator preserves
     Hermiticity, and the Hermitian kernels keep it exact at every stage.
+
+    Hermitian batches of 208 matrices or more at 64 < N <= 128 with collapse operators, no snapshots and at least
+    EIG_MIN_STEPS steps are propagated in the eigenbasis of A = -iH - 1/2 sum C^+ C (qd_lindblad_rk4_eig, 100 instead of
+    164 tile-GEMMs per stage).  A is diagonalised once per (H, c_ops) on the host (about 20 to 40 ms, cached like the
+    Hermiticity check, with e_ops); operators whose eigenvector matrix is ill-conditioned (EIG_MAX_COND) keep the
+    persistent kernel, as does a call captured into a graph before its plan exists.  Results differ from the persistent
+    kernel's in rounding (1e-14 relative at the benchmark's operators); the library option glf_path "persistent"
+    keeps that kernel, "eig" takes the eigenbasis path at any batch size.
     """
     squeeze = rho.dim() == 2
     if squeeze:
@@ -104,14 +239,36 @@ def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor,
     # X + X^+ equals the reference's -i[H, rho] + D[rho] only for Hermitian H and rho (oqs.py:697-714 uses
     # rho H, not rho H^+), so the Hermitian kernel is gated on both, bit for bit.
     h_herm = _is_hermitian_cached(H)
+    glf_path = _lib.get_option(_lib.QD_OPT_GLF_PATH)
+    eig_forced = glf_path == _lib.GLF_PATHS["eig"]
     if hermitian is None:
         min_b = HERM_NP64_MIN_BATCH if 32 < N <= 64 else HERM_SPLIT_MIN_BATCH
         # one or two trajectories at N_p = 128 with 1 or 2 collapse operators: the Hermitian single launch
         single_h = 64 < N <= 128 and B <= 2 and 1 <= nc <= 2
-        hermitian = (N <= 128 and (B >= min_b or single_h) and h_herm
+        hermitian = (N <= 128 and (B >= min_b or single_h or eig_forced) and h_herm
                      and bool(torch.equal(rho, rho.transpose(-1, -2).conj())))
     elif hermitian and not h_herm:
         raise ValueError("hermitian=True needs a Hermitian H (the X + X^+ form drops the anti-Hermitian part of H)")
+    # Eigenbasis path (qd_lindblad_rk4_eig): the Hermitian gate above, 64 < N <= 128, collapse operators, no snapshots,
+    # and the batch sizes at which the library would run the persistent kernel; glf_path "eig" takes it at any batch
+    # size and raises when the call cannot run on it; "persistent" (or any other forced path) keeps the other kernels.
+    # A plan refused by its guards, or not yet cached while the stream is capturing, leaves the call where it was.
+    eig_ok = bool(hermitian) and 64 < N <= EIG_NP and 1 <= nc <= EIG_MAX_NC and not nsave
+    if eig_forced and not eig_ok:
+        raise ValueError('glf_path "eig" needs Hermitian H and rho, 64 < N <= 128, 1 <= nc <= 256 and no snapshots; '
+                         f"got hermitian={bool(hermitian)}, N={N}, nc={nc}, save_every={save_every}")
+    if eig_ok and nsteps >= 1 and (eig_forced or (glf_path == _lib.GLF_PATHS["auto"] and B >= EIG_MIN_BATCH
+                                                  and nsteps >= EIG_MIN_STEPS)):
+        got = _eig_plan_cached(H, c_ops, e_ops)
+        if got is not None:
+            ent, Et = got
+            lam, V, Vinv, Ct = ent.dev
+            with torch.cuda.device(dev):
+                rc = _lib.load().qd_lindblad_rk4_eig(_lib.ptr(lam), _lib.ptr(V), _lib.ptr(Vinv), _lib.ptr(Ct), nc,
+                                                     _lib.ptr(rho), B, N, float(dt), int(nsteps), _lib.ptr(Et), ne,
+                                                     _lib.ptr(obs), st)
+            _lib.check(rc, "qd_lindblad_rk4_eig")
+            return obs, None
     fn = "qd_lindblad_rk4_herm" if hermitian else "qd_lindblad_rk4"
     with torch.cuda.device(dev):
         rc = getattr(_lib.load(), fn)(_lib.ptr(H), _lib.ptr(c_ops), nc, _lib.ptr(rho), B, N, float(dt),
