@@ -166,45 +166,13 @@ __device__ __forceinline__ void ens_x_uniform_block(int bx, int by, const c128* 
   }
 }
 
-// Z rows of member m = blockIdx.y, uniform t1: tables of e^{lam_q t} in LDS (nL x (16 + n1p/16)).
-constexpr int UNI_MAXC = 1024 / 16;
-// One launch, both operands: blockIdx.y < M -> Z rows of member blockIdx.y (blockIdx.x = column
-// block); blockIdx.y >= M -> X block (blockIdx.y - M) in a (Kp/256) x (n3p/XU_ROWS) tiling.
-__global__ __launch_bounds__(256) void ens_xz_uniform_kernel(const c128* Mt, const c128* beta, const c128* lam, int M,
-                                                             int nL, double t0, double dt, int n1, int n1p, int Kp,
-                                                             c128* Z, const c128* alpha, int K, double t3_0,
-                                                             double dt3, int n3, int n3p, int xbx, c128* X, int nz,
-                                                             const c128* lamz) {
-  __shared__ c128 sM[ZMAX * ZMAX];
-  __shared__ c128 sF[ZMAX * 16];        // e^{lam_q j dt}
-  __shared__ c128 sC[ZMAX * UNI_MAXC];  // beta_q e^{lam_q (t0 + 16 l dt)}
-  if ((int)blockIdx.y >= M) {
-    if (blockIdx.x != 0) return;
-    const int xb = blockIdx.y - M;
-    ens_x_uniform_block(xb % xbx, xb / xbx, alpha, lam, K, Kp, t3_0, dt3, n3, n3p, X);
-    return;
-  }
-  const int m = blockIdx.y;
-  const int nC = n1p / 16;
-  const c128* lm = lamz + (size_t)m * nz;
-  for (int e = threadIdx.x; e < nL * nz; e += 256) sM[e] = Mt[(size_t)m * nL * nz + e];
-  for (int e = threadIdx.x; e < nz * 16; e += 256) sF[e] = cexp_t(lm[e / 16], (double)(e % 16) * dt);
-  for (int e = threadIdx.x; e < nz * nC; e += 256)
-    sC[e] = cmul(beta[(size_t)m * nz + e / nC], cexp_t(lm[e / nC], t0 + 16.0 * (double)(e % nC) * dt));
-  __syncthreads();
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= n1p) return;
-  c128 y[ZMAX];
-#pragma unroll
-  for (int q = 0; q < ZMAX; ++q)
-    y[q] = (q < nz && k < n1) ? cmul(sC[q * nC + (k >> 4)], sF[q * 16 + (k & 15)]) : cmk(0, 0);
-  for (int p = 0; p < nL; ++p) {
-    c128 v = cmk(0, 0);
-#pragma unroll
-    for (int q = 0; q < ZMAX; ++q)
-      if (q < nz) v = cadd(v, cmul(sM[p * nz + q], y[q]));
-    Z[((size_t)m * nL + p) * n1p + k] = v;
-  }
+constexpr int UNI_MAXC = 1024 / 16;  // coarse-table entries of a uniform t1 grid (n1p <= 1024)
+// Materialised uniform X in a launch of its own: block blockIdx.x of the (Kp/256) x (n3p/XU_ROWS) tiling.  The block
+// index runs along x, whose extent is not bound by the 65,535 of a grid's y.
+__global__ __launch_bounds__(256) void ens_x_uniform_kernel(const c128* alpha, const c128* lam, int K, int Kp,
+                                                            double t3_0, double dt3, int n3, int n3p, int xbx,
+                                                            c128* X) {
+  ens_x_uniform_block(blockIdx.x % xbx, blockIdx.x / xbx, alpha, lam, K, Kp, t3_0, dt3, n3, n3p, X);
 }
 
 // Z rows of G members per block (uniform t1), tables in dynamic LDS: per member Mt_m (nL x nz), the fine
@@ -778,14 +746,22 @@ int ens_run(const char* fn, const qd_c128* alpha, const qd_c128* Mt, const qd_c1
   }
   const int G = z_group(nL, nz, n1p, M);
   const int nMB = ceil_div(M, G);
-  if (!t1 && nL <= ZMAX && nz <= ZMAX && n1p <= 16 * UNI_MAXC && (long)nMB + xblocks <= 65535) {
+  const bool xin = !t3 && !xtab;  // uniform t3, X materialised
+  if (!t1 && nL <= ZMAX && nz <= ZMAX && n1p <= 16 * UNI_MAXC && nMB <= 65535) {
     // Z (uniform t1), G members per block; a materialised uniform X (when not generated in the GEMM) in
-    // the same launch
-    const bool xin = !t3 && !xtab;
-    hipLaunchKernelGGL(ens_z_uniform_kernel, dim3(zbx, nMB + (xin ? xblocks : 0)), dim3(256),
+    // the same launch while the grid's y extent holds both, else in a launch of its own
+    const bool xsame = xin && (long)nMB + xblocks <= 65535;
+    note_path("ens_z_uniform");
+    hipLaunchKernelGGL(ens_z_uniform_kernel, dim3(zbx, nMB + (xsame ? xblocks : 0)), dim3(256),
                        z_lds(G, nL, nz, n1p), st, (const c128*)Mt, (const c128*)beta, lamz, M, nL, nz, G, t1_0,
                        dt1, n1, n1p, Z, (const c128*)alpha, (const c128*)lam, K, Kp, t3_0, dt3, n3, n3p, xbx, X);
     QD_HIP(hipGetLastError());
+    if (xin && !xsame) {
+      note_path("ens_x_uniform_own");
+      hipLaunchKernelGGL(ens_x_uniform_kernel, dim3(xblocks), dim3(256), 0, st, (const c128*)alpha, (const c128*)lam,
+                         K, Kp, t3_0, dt3, n3, n3p, xbx, X);
+      QD_HIP(hipGetLastError());
+    }
     if (Kp > K) {
       hipLaunchKernelGGL(ens_z_pad_kernel, dim3(64), dim3(256), 0, st, K, Kp, n1p, Z);
       QD_HIP(hipGetLastError());
@@ -796,13 +772,14 @@ int ens_run(const char* fn, const qd_c128* alpha, const qd_c128* Mt, const qd_c1
       QD_HIP(hipGetLastError());
     }
   } else {
-    QD_CHECK_ARG(t1, "%s: uniform t1 needs nL <= %d and n1 <= %d", fn, ZMAX, 16 * UNI_MAXC);
-    if (!t3 && !xtab) {  // uniform t3 with an array t1: X blocks only
-      hipLaunchKernelGGL(ens_xz_uniform_kernel, dim3(1, xblocks), dim3(256), 0, st, (const c128*)Mt,
-                         (const c128*)beta, (const c128*)lam, 0, nL, 0.0, 0.0, n1, n1p, Kp, Z, (const c128*)alpha, K,
-                         t3_0, dt3, n3, n3p, xbx, X, nz, lamz);
+    QD_CHECK_ARG(t1, "%s: uniform t1 needs nL <= %d, n1 <= %d and at most 65535 member groups (M = %d makes %d)", fn,
+                 ZMAX, 16 * UNI_MAXC, M, nMB);
+    if (xin) {  // uniform t3 with an array t1: X blocks only
+      hipLaunchKernelGGL(ens_x_uniform_kernel, dim3(xblocks), dim3(256), 0, st, (const c128*)alpha, (const c128*)lam,
+                         K, Kp, t3_0, dt3, n3, n3p, xbx, X);
       QD_HIP(hipGetLastError());
     }
+    note_path(zfast ? "ens_z_array" : "ens_z_generic");
     if (zfast) {
       // X (when from an array) gets as many block rows as Z has (capped): one launch, both writes
       const int xrows = t3 ? std::max(1, std::min(M, 4096)) : 0;
