@@ -1,15 +1,25 @@
-// wp_gmat_kernels.hpp — kernels of the curvilinear (G-matrix) wavepacket propagator (wp_gmat.hip), psi [B][nx][ny]
-// (on coupled surfaces [B][ns][nx][ny], below).
+// wp_gmat_kernels.hpp — kernels of the curvilinear (G-matrix) wavepacket propagator (wp_gmat.hip) in two and three
+// coordinates, psi [B][nx][ny] or [B][nx][ny][nz] (on coupled surfaces [B][ns][...], below).
 //
-//   D_x f = IFFT_x(kx FFT_x f)     D_y f = IFFT_y(ky FFT_y f)      (1/n folded into the k tables)
-//   phi_x = Gxx D_x y + Gxy D_y y   phi_y = Gyx D_x y + Gyy D_y y
-//   H y   = 1/2 (D_x phi_x + D_y phi_y) + v y
+//   D_a f   = IFFT_a(k_a FFT_a f)                                  (1/n folded into the k tables)
+//   phi_r   = sum_s G_rs D_s y                                     (summed from the x term, s ascending)
+//   H y     = 1/2 (D_x phi_x + D_y phi_y) + v y                    in two coordinates,
+//             1/2 ((D_x phi_x + D_y phi_y) + D_z phi_z) + v y      in three
 //
-// Power-of-two grids: two fused passes per application of H, every transform on LDS (fft_lds<L, INV>).
+// Two coordinates, power-of-two grids: two fused passes per application of H, every transform on LDS
+// (fft_lds<L, INV>).
 //   column pass (x, strided axis): a tile of C columns, each tile row one C x 16 B segment; y and D_y y in,
 //                                  u = D_x phi_x and phi_y out
 //   row pass (y, contiguous axis): R whole rows; D_y phi_y, H y, the Horner update, and D_y of the new state
-// Any other grid: element-wise kernels around fft_lines (qd_common.hpp).
+// Three coordinates, powers of two in [16, 256] on every axis: every pass a kernel over an [O][L][I] view of the grid.
+//   X  (L = nx, I = ny nz)   y, D_y y, D_z y and the nine metric entries in; D_x y, then phi_x, formed in LDS;
+//                            u = D_x phi_x, phi_y, phi_z out
+//   Y  (L = ny, I = nz)      u += D_y phi_y in place (ACC), or dst = D_y src (the prologue and the pass behind Z)
+//   Z  (L = nz, I = 1)       whole lines: the row pass over nx ny rows of nz points, which is the same arithmetic
+//                            (D phi, H y, the Horner update, D of the new state)
+// X and Y take strided tiles of C = min(16, 1024 / L) consecutive inner indices, 4 points per thread, LDS lines padded
+// to L + 1 (the stores transpose).  L <= 256 keeps C >= 4: a tile row is at least one 64 B segment.
+// Any other grid: element-wise kernels, templates on the number of coordinates, around fft_lines (qd_common.hpp).
 //
 // Coupled surfaces: psi [B][ns][nx][ny], the states as planes, so every pass sees B ns members; the potential
 // V [ns][ns][nx][ny], and v y of plane a becomes sum_b V_ab y_b (b ascending from V_a0 y_0, added to the kinetic half
@@ -129,7 +139,7 @@ __global__ __launch_bounds__(C * L / 4) void wp2_gmat_col_kernel(const c128* y, 
 //   WPG_STAGE: ynew = psi - i coef (1/2 (u + D_y phy) + sum_b V_ab ys_b), also to snap when given; dy = D_y ynew
 // ynew may be psi (read at the thread's own plane and points only).  ynew may be ys for ns = 1 alone: a thread reads
 // the points it writes before it writes them, but the planes b != a of ys belong to other workgroups.
-// wp_gmat3.hip instantiates this kernel too, as its Z pass over nx ny rows of nz points: a change here changes its bits.
+// In three coordinates this kernel is the Z pass, over nx ny rows of nz points: a change here changes those bits too.
 enum WpgRowMode { WPG_PRO = 0, WPG_APPLY = 1, WPG_STAGE = 2 };
 
 template <int L, int MODE>
@@ -201,6 +211,103 @@ __global__ __launch_bounds__(wpg_row_r(L) * L / 4) void wp2_gmat_row_kernel(cons
   for (int n = 0; n < 4; ++n) dy[po + tid + n * BD] = cur[tid + n * BD];
 }
 
+// ---------------------------------------------------------------- three coordinates: the X and Y passes
+constexpr int wpg3_c(int L) { return L <= 64 ? 16 : 1024 / L; }
+constexpr bool wpg3_pow2(int n) { return n >= 16 && n <= 256 && (n & (n - 1)) == 0; }
+
+// X pass over the tile of C inner indices i0 .. i0 + C - 1 of member m (blockIdx.x = m (I / C) + i0 / C), L = nx,
+// I = ny nz (a multiple of C).  The metric is indexed by the point within the member.
+template <int L>
+__global__ __launch_bounds__(wpg3_c(L) * L / 4) void wp3_gmat_x_kernel(const c128* y, const c128* dy, const c128* dz,
+                                                                       const double* G, const c128* twx,
+                                                                       const double* kxs, long I, c128* u, c128* phy,
+                                                                       c128* phz) {
+  constexpr int C = wpg3_c(L), LP = L + 1, BD = C * L / 4;
+  __shared__ c128 tw[L], A[C * LP], Bf[C * LP];
+  __shared__ double ks[L];
+  const int tid = threadIdx.x;
+  const long nblk = I / C;
+  const long m = blockIdx.x / nblk, i0 = (blockIdx.x % nblk) * C;
+  const size_t mo = (size_t)m * L * I;
+  c128 yv[4], dyv[4], dzv[4];
+  double g[4][9];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {   // element e: tile row e / C, inner index e % C
+    const int e = tid + n * BD;
+    const size_t p = (size_t)(e / C) * I + i0 + e % C;
+    yv[n] = y[mo + p];
+    dyv[n] = dy[mo + p];
+    dzv[n] = dz[mo + p];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) g[n][q] = G[9 * p + q];
+  }
+  for (int k = tid; k < L; k += BD) {
+    tw[k] = twx[k];
+    ks[k] = kxs[k];
+  }
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int e = tid + n * BD;
+    A[(e % C) * LP + e / C] = yv[n];
+  }
+  __syncthreads();
+  c128* cur = wpg_deriv<L, LP, C>(A, Bf, tw, ks, tid);
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {   // every thread rewrites the slots it reads: no barrier between
+    const int e = tid + n * BD, a = (e % C) * LP + e / C;
+    const size_t p = (size_t)(e / C) * I + i0 + e % C;
+    const c128 dx = cur[a];
+    phy[mo + p] = cadd(cadd(cscale(dx, g[n][3]), cscale(dyv[n], g[n][4])), cscale(dzv[n], g[n][5]));
+    phz[mo + p] = cadd(cadd(cscale(dx, g[n][6]), cscale(dyv[n], g[n][7])), cscale(dzv[n], g[n][8]));
+    cur[a] = cadd(cadd(cscale(dx, g[n][0]), cscale(dyv[n], g[n][1])), cscale(dzv[n], g[n][2]));
+  }
+  __syncthreads();
+  cur = wpg_deriv<L, LP, C>(cur, cur == A ? Bf : A, tw, ks, tid);
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int e = tid + n * BD;
+    u[mo + (size_t)(e / C) * I + i0 + e % C] = cur[(e % C) * LP + e / C];
+  }
+}
+
+// Y pass over the tile of C inner indices of outer index o (blockIdx.x = o (I / C) + i0 / C) of the [O][L][I] view,
+// L = ny, I = nz:  ACC: dst += D src (a thread reads the slots of dst it writes before it writes them);  else
+// dst = D src.
+template <int L, bool ACC>
+__global__ __launch_bounds__(wpg3_c(L) * L / 4) void wp3_gmat_y_kernel(const c128* src, const c128* twy,
+                                                                       const double* kys, int I, c128* dst) {
+  constexpr int C = wpg3_c(L), LP = L + 1, BD = C * L / 4;
+  __shared__ c128 tw[L], A[C * LP], Bf[C * LP];
+  __shared__ double ks[L];
+  const int tid = threadIdx.x, nblk = I / C;
+  const size_t oo = (size_t)(blockIdx.x / nblk) * L * I + (size_t)(blockIdx.x % nblk) * C;
+  c128 sv[4], uv[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int e = tid + n * BD;
+    const size_t p = oo + (size_t)(e / C) * I + e % C;
+    sv[n] = src[p];
+    uv[n] = ACC ? dst[p] : cmk(0, 0);
+  }
+  for (int k = tid; k < L; k += BD) {
+    tw[k] = twy[k];
+    ks[k] = kys[k];
+  }
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int e = tid + n * BD;
+    A[(e % C) * LP + e / C] = sv[n];
+  }
+  __syncthreads();
+  const c128* cur = wpg_deriv<L, LP, C>(A, Bf, tw, ks, tid);
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int e = tid + n * BD;
+    const c128 d = cur[(e % C) * LP + e / C];
+    dst[oo + (size_t)(e / C) * I + e % C] = ACC ? cadd(uv[n], d) : d;
+  }
+}
+
 // ---------------------------------------------------------------- any grid: element-wise kernels around fft_lines
 // dst[o][k][i] = s[k] src[o][pos(k)][i] over the [O][L][I] grid of n points: pos(k) the slot of bin k in fft_lines'
 // output (four-step order when l2 != 0, else k itself); s null: the reordering alone.
@@ -217,21 +324,36 @@ __global__ void wpg_pick_kernel(const c128* __restrict__ src, c128* __restrict__
   }
 }
 
-// (a, b) <- (Gxx a + Gxy b, Gyx a + Gyy b) per point of every member (npts points per member)
-__global__ void wpg_gprod_kernel(c128* a, c128* b, const double* __restrict__ G, long n, long npts) {
+// One state-sized array per coordinate
+template <int D>
+struct WpgVec {
+  c128* p[D];
+};
+
+// d <- G d per point of every member (npts points per member), G [npts][D][D], each row summed from its x term
+template <int D>
+__global__ void wpg_gprod_kernel(WpgVec<D> d, const double* __restrict__ G, long n, long npts) {
   for (long f = blockIdx.x * (long)blockDim.x + threadIdx.x; f < n; f += (long)gridDim.x * blockDim.x) {
-    const double* g = G + 4 * (f % npts);
-    const c128 dx = a[f], dv = b[f];
-    a[f] = cadd(cscale(dx, g[0]), cscale(dv, g[1]));
-    b[f] = cadd(cscale(dx, g[2]), cscale(dv, g[3]));
+    const double* g = G + D * D * (f % npts);
+    c128 in[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) in[s] = d.p[s][f];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      c128 phi = cadd(cscale(in[0], g[D * r]), cscale(in[1], g[D * r + 1]));
+#pragma unroll
+      for (int s = 2; s < D; ++s) phi = cadd(phi, cscale(in[s], g[D * r + s]));
+      d.p[r][f] = phi;
+    }
   }
 }
 
-// h = 1/2 (u + w) + sum_b V_ab ys_b over the [B ns] planes of npts points (plane f / npts = m ns + a; v null: no
-// potential);  psi null: ynew = h;  else ynew = psi - i coef h (also to snap when given).  ynew may be ys for ns = 1
-// alone.
-__global__ void wpg_combine_kernel(const c128* u, const c128* w, const c128* ys, const c128* psi, const c128* v,
-                                   long n, long npts, int ns, double coef, c128* ynew, c128* snap, size_t sstride) {
+// h = 1/2 (u_x + u_y (+ u_z)) + sum_b V_ab ys_b, the kinetic terms summed from u_x, over the [B ns] planes of npts
+// points (plane f / npts = m ns + a; v null: no potential);  psi null: ynew = h;  else ynew = psi - i coef h (also to
+// snap when given).  ynew may be ys for ns = 1 alone.
+template <int D>
+__global__ void wpg_combine_kernel(WpgVec<D> u, const c128* ys, const c128* psi, const c128* v, long n, long npts,
+                                   int ns, double coef, c128* ynew, c128* snap, size_t sstride) {
   for (long f = blockIdx.x * (long)blockDim.x + threadIdx.x; f < n; f += (long)gridDim.x * blockDim.x) {
     const long mp = f / npts, p = f - mp * npts;
     const int sa = (int)(mp % ns);
@@ -242,7 +364,10 @@ __global__ void wpg_combine_kernel(const c128* u, const c128* w, const c128* ys,
       vy = wpg_vy_any(vb[0], yb[0]);
       for (int b = 1; b < ns; ++b) vy = cadd(vy, wpg_vy_any(vb[(size_t)b * npts], yb[(size_t)b * npts]));
     }
-    const c128 h = cadd(cscale(cadd(u[f], w[f]), 0.5), vy);
+    c128 k = cadd(u.p[0][f], u.p[1][f]);
+#pragma unroll
+    for (int s = 2; s < D; ++s) k = cadd(k, u.p[s][f]);
+    const c128 h = cadd(cscale(k, 0.5), vy);
     if (!psi) {
       ynew[f] = h;
       continue;

@@ -9,7 +9,9 @@ Populations, mean positions and the electronic reduced density matrix are reduce
 Curvilinear coordinates (wpd.py:1783-1940: adiabatic_2d, KEO, PEO, hpsi) apply the G-matrix kinetic operator and run
 its RK4 steps in libqdyn (qd_wp2_gmat_apply / qd_wp2_gmat_rk4); on coupled surfaces (a potential [nx, ny, ns, ns];
 SPO2(coords='curvilinear', G=G)) qd_wp2_gmat_ms_apply / qd_wp2_gmat_ms_rk4; in three coordinates (KEO3, hpsi3,
-curvilinear_run3, SPO3(coords='curvilinear', G=G) with G [nx, ny, nz, 3, 3]) the qd_wp3_gmat_* calls.
+curvilinear_run3, SPO3(coords='curvilinear', G=G) with G [nx, ny, nz, 3, 3]) the qd_wp3_gmat_* calls.  One front
+serves all of them: _gmat_check, _gmat_dev, _gmat_apply and _gmat_run take the k vectors or axes as a list, and the
+number of coordinates and of states names the entry point (_gmat_call).
 """
 from __future__ import annotations
 
@@ -476,7 +478,7 @@ class SPO2(_PointPropagators):
         self.kx = 2. * np.pi * fftfreq(nx, interval(self.x))
         self.ky = 2. * np.pi * fftfreq(ny, interval(self.y))
         if self.coords == 'curvilinear':   # RK4 on the G-matrix operator: no exp_K, no exp_V
-            _gmat_check_G(self.G, nx, ny, f"the grid {(nx, ny)}")
+            _gmat_check_G(self.G, (nx, ny), f"the grid {(nx, ny)}")
             self._d2a = self._apes = self._d2a_dev = None
             self._eig_pending = self.v is not None   # d2a for observe='adiabatic': host eigh on first access
             return
@@ -887,7 +889,7 @@ class SPO3(_PointPropagators):
                 raise NotImplementedError("SPO3 with coords='curvilinear' needs a 3-D metric G [nx, ny, nz, 3, 3]; two "
                                           "curvilinear coordinates with a rectilinear third (a four-dimensional G "
                                           f"{_shape_of(self.G)}) are not built")
-            _gmat3_check_G(self.G, *dims, f"the grid {dims}")
+            _gmat_check_G(self.G, dims, f"the grid {dims}")
             self.kx, self.ky, self.kz = (_gmat_k(n, a) for n, a in zip(dims, self._axes()))
             self._d2a = self._apes = self._d2a_dev = None
             self._eig_pending = self.V is not None   # d2a for observe='adiabatic': host eigh on first access
@@ -1027,110 +1029,122 @@ def _is_complex_nonzero(a):
     return np.iscomplexobj(a) and bool(np.any(np.imag(a) != 0))
 
 
-def _gmat_check(psi, G, v, nkx, nky):
-    """Shape and type checks of a curvilinear call, before any device call for ndarray and host-tensor operands (a
-    complex G held on the device is tested there).  Returns (nx, ny, batched)."""
-    shape = tuple(psi.shape) if isinstance(psi, torch.Tensor) else np.shape(psi)
-    if len(shape) not in (2, 3):
-        raise ValueError(f"psi must be [nx, ny] or a batch [B, nx, ny]; got {shape}")
-    nx, ny = int(shape[-2]), int(shape[-1])
-    _gmat_check_G(G, nx, ny, f"psi {shape}")
-    if v is not None:
-        vshape = tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)
-        if vshape != (nx, ny):
-            raise ValueError(f"v must be {(nx, ny)} for psi {shape}; got {vshape}")
-    if (nkx, nky) != (nx, ny):
-        raise ValueError(f"kx, ky have lengths {(nkx, nky)}; psi {shape} needs {(nx, ny)}")
-    return nx, ny, len(shape) == 3
+_AXES = ("nx", "ny", "nz")
 
 
-def _gmat_check_G(G, nx, ny, what):
+def _shape_of(a):
+    return tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+
+
+def _gmat_k(n, axis):
+    """k = 2 pi fftfreq(n, d) of an axis of n points, zeros(1) for an axis of length 1."""
+    return 2. * np.pi * fftfreq(n, interval(axis)) if n > 1 else np.zeros(1)
+
+
+def _gmat_check_G(G, dims, what):
+    D = len(dims)
     if G is None:
-        raise ValueError("curvilinear coordinates need the metric G [nx, ny, 2, 2]")
-    gshape = tuple(G.shape) if isinstance(G, torch.Tensor) else np.shape(G)
-    if gshape != (nx, ny, 2, 2):
-        raise ValueError(f"G must be {(nx, ny, 2, 2)} for {what}; got {gshape}")
+        raise ValueError(f"curvilinear coordinates need the metric G [{', '.join(_AXES[:D])}, {D}, {D}]")
+    if _shape_of(G) != dims + (D, D):
+        raise ValueError(f"G must be {dims + (D, D)} for {what}; got {_shape_of(G)}")
     if _is_complex_nonzero(G):
         raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
 
 
-def _is_ms(v):
-    """A 4-D potential [nx, ny, ns, ns] selects the coupled-surface operator."""
-    return v is not None and len(tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)) == 4
+def _gmat_check(psi, G, v, nk):
+    """Shape and type checks of a curvilinear call in D = len(nk) coordinates, before any device call for ndarray and
+    host-tensor operands (a complex G held on the device is tested there).  With `grid` the D extents, v [grid] (or
+    None) takes psi [grid] or a batch [B, grid]; v [grid, ns, ns] takes psi [grid, ns] or [B, grid, ns].  Returns
+    (dims, ns, batched), ns = 0 on a single surface."""
+    D = len(nk)
+    grid = ", ".join(_AXES[:D])
+    shape = _shape_of(psi)
+    vshape = None if v is None else _shape_of(v)
+    if vshape is not None and len(vshape) == D + 2:
+        want = f"v [{grid}, ns, ns] needs psi [{grid}, ns] or a batch [B, {grid}, ns]"
+        if len(shape) not in (D + 1, D + 2):
+            raise ValueError(f"{want}; got psi {shape}")
+        dims, ns = tuple(int(n) for n in shape[-D - 1:-1]), int(vshape[-1])
+        if vshape != dims + (ns, ns) or ns < 1:
+            raise ValueError(f"v must be [{grid}, ns, ns] = {dims} + (ns, ns) for psi {shape}; got {vshape}")
+        if int(shape[-1]) != ns:
+            raise ValueError(f"{want}: v {vshape} has ns = {ns}; got psi {shape}")
+        batched = len(shape) == D + 2
+    else:
+        if len(shape) not in (D, D + 1):
+            raise ValueError(f"psi must be [{grid}] or a batch [B, {grid}]; got {shape}")
+        dims, ns, batched = tuple(int(n) for n in shape[-D:]), 0, len(shape) == D + 1
+        if vshape is not None and vshape != dims:
+            raise ValueError(f"v must be {dims} (or [{grid}, ns, ns]) for psi {shape}; got {vshape}")
+    _gmat_check_G(G, dims, f"psi {shape}")
+    if tuple(nk) != dims:
+        raise ValueError(f"{', '.join('k' + a[1] for a in _AXES[:D])} have lengths {tuple(nk)}; psi {shape} needs "
+                         f"{dims}")
+    return dims, ns, batched
 
 
-def _gmat_check_ms(psi, G, v, nkx, nky):
-    """_gmat_check for coupled surfaces: v [nx, ny, ns, ns], psi [nx, ny, ns] or a batch [B, nx, ny, ns].  Returns
-    (nx, ny, ns, batched)."""
-    shape = tuple(psi.shape) if isinstance(psi, torch.Tensor) else np.shape(psi)
-    vshape = tuple(v.shape) if isinstance(v, torch.Tensor) else np.shape(v)
-    want = "v [nx, ny, ns, ns] needs psi [nx, ny, ns] or a batch [B, nx, ny, ns]"
-    if len(shape) not in (3, 4):
-        raise ValueError(f"{want}; got psi {shape}")
-    nx, ny, ns = int(shape[-3]), int(shape[-2]), int(vshape[-1])
-    if vshape != (nx, ny, ns, ns) or ns < 1:
-        raise ValueError(f"v must be [nx, ny, ns, ns] = {(nx, ny)} + (ns, ns) for psi {shape}; got {vshape}")
-    if int(shape[-1]) != ns:
-        raise ValueError(f"{want}: v {vshape} has ns = {ns}; got psi {shape}")
-    _gmat_check_G(G, nx, ny, f"psi {shape}")
-    if (nkx, nky) != (nx, ny):
-        raise ValueError(f"kx, ky have lengths {(nkx, nky)}; psi {shape} needs {(nx, ny)}")
-    return nx, ny, ns, len(shape) == 4
-
-
-def _gmat_dev_ms(psi, G, v, kx, ky):
-    """_gmat_dev for coupled surfaces, in the kernels' plane layout: psi [B, ns, nx, ny] (always a copy) and
-    V [ns, ns, nx, ny], permuted on the device."""
-    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi, G, v, kx, ky)
-    if t.dim() == 3:
-        t = t[None]
-    planes = t.permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format)   # contiguous() copies nothing at ns = 1
-    return dev, planes, Gd, vd.permute(2, 3, 0, 1).contiguous(), kxd, kyd
-
-
-def _gmat_dev(psi, G, v, kx, ky):
-    """Device operands: psi [B, nx, ny] (a contiguous complex128 device tensor is used in place, not copied), G float64,
-    v complex128 or None, kx, ky float64."""
+def _gmat_dev(psi, G, v, ks, ns, copy=False):
+    """Device operands in the kernels' plane layout: psi [B, max(ns, 1), *dims], G float64, V [ns, ns, *dims] or
+    v [*dims] complex128 or None, and the k vectors float64.  On a single surface a contiguous complex128 device tensor
+    is used in place, not copied (its state axis of size 1 is a view); copy=True makes the planes a tensor of their
+    own, for a run, which advances them in place."""
     dev = psi.device if isinstance(psi, torch.Tensor) and psi.device.type == "cuda" else default_device()
     _lib.ensure_device(dev)
-    t = psi.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(psi, torch.Tensor) \
-        else _dev_c128(psi, dev)
-    if t.dim() == 2:
+    t = psi.to(device=dev, dtype=torch.complex128) if isinstance(psi, torch.Tensor) else _dev_c128(psi, dev)
+    if t.dim() == len(ks) + (1 if ns else 0):
         t = t[None]
+    t = t.movedim(-1, 1) if ns else t[:, None]
+    t = t.clone(memory_format=torch.contiguous_format) if copy else t.contiguous()
     if isinstance(G, torch.Tensor):
         Gd = (G.real if G.is_complex() else G).to(device=dev, dtype=torch.float64).contiguous()
     else:
         Gd = _dev_f64(np.real(G), dev)
     vd = None
     if v is not None:
-        vd = v.to(device=dev, dtype=torch.complex128).contiguous() if isinstance(v, torch.Tensor) else _dev_c128(v, dev)
+        vd = v.to(device=dev, dtype=torch.complex128) if isinstance(v, torch.Tensor) else _dev_c128(v, dev)
+        vd = (vd.movedim((-2, -1), (0, 1)) if ns else vd).contiguous()
     f64 = lambda k: k.to(device=dev, dtype=torch.float64).contiguous() if isinstance(k, torch.Tensor) \
         else _dev_f64(k, dev)
-    return dev, t, Gd, vd, f64(kx), f64(ky)
+    return dev, t, Gd, vd, [f64(k) for k in ks]
 
 
-def _gmat_apply(psi, kx, ky, v, G):
-    """(K + v) psi on the device (qd_wp2_gmat_apply, or qd_wp2_gmat_ms_apply for v [nx, ny, ns, ns]); returns a device
-    tensor shaped like psi."""
-    if _is_ms(v):
-        nx, ny, ns, batched = _gmat_check_ms(psi, G, v, len(kx), len(ky))
-        dev, t, Gd, vd, kxd, kyd = _gmat_dev_ms(psi, G, v, kx, ky)
-        out = torch.empty_like(t)
-        with torch.cuda.device(dev):
-            rc = _lib.load().qd_wp2_gmat_ms_apply(t.data_ptr(), int(t.shape[0]), ns, Gd.data_ptr(), vd.data_ptr(),
-                                                  kxd.data_ptr(), kyd.data_ptr(), nx, ny, out.data_ptr(),
-                                                  _lib.stream_ptr(dev))
-        _lib.check(rc, "qd_wp2_gmat_ms_apply")
-        out = out.permute(0, 2, 3, 1).contiguous()
-        return out if batched else out[0]
-    nx, ny, batched = _gmat_check(psi, G, v, len(kx), len(ky))
-    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi, G, v, kx, ky)
-    out = torch.empty_like(t)
+def _gmat_call(what, dev, t, ns, Gd, vd, kd, dims, *tail):
+    """qd_wp{D}_gmat[_ms]_{what} on the planes t [B, max(ns, 1), *dims]: D and ns name the entry point."""
+    name = f"qd_wp{len(dims)}_gmat{'_ms' if ns else ''}_{what}"
+    head = (t.data_ptr(), int(t.shape[0])) + ((ns,) if ns else ())
     with torch.cuda.device(dev):
-        rc = _lib.load().qd_wp2_gmat_apply(t.data_ptr(), int(t.shape[0]), Gd.data_ptr(), _lib.ptr(vd), kxd.data_ptr(),
-                                           kyd.data_ptr(), nx, ny, out.data_ptr(), _lib.stream_ptr(dev))
-    _lib.check(rc, "qd_wp2_gmat_apply")
+        rc = getattr(_lib.load(), name)(*head, Gd.data_ptr(), _lib.ptr(vd), *(k.data_ptr() for k in kd), *dims, *tail,
+                                        _lib.stream_ptr(dev))
+    _lib.check(rc, name)
+
+
+def _gmat_apply(psi, ks, v, G):
+    """(K + v) psi on the device in len(ks) coordinates (qd_wp{2,3}_gmat_apply, or the _ms_apply call for
+    v [grid, ns, ns]); returns a device tensor shaped like psi."""
+    dims, ns, batched = _gmat_check(psi, G, v, [len(k) for k in ks])
+    dev, t, Gd, vd, kd = _gmat_dev(psi, G, v, ks, ns)
+    out = torch.empty_like(t)
+    _gmat_call("apply", dev, t, ns, Gd, vd, kd, dims, out.data_ptr())
+    out = out.movedim(1, -1).contiguous() if ns else out[:, 0]
     return out if batched else out[0]
+
+
+def _gmat_run(axes, psi0s, v, G, dt, nt, nout):
+    """(nt // nout) nout RK4 steps on the coordinate arrays `axes` (qd_wp{2,3}_gmat_rk4, or the _ms_rk4 call for
+    v [grid, ns, ns]): device tensors (final states [B, grid], snapshots [B, nt // nout, grid]), with a trailing state
+    axis on coupled surfaces.  psi0s is not modified."""
+    if nout < 1 or nt < 0:
+        raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
+    dims, ns, _ = _gmat_check(psi0s, G, v, [len(a) for a in axes])
+    ks = [_gmat_k(n, a) for n, a in zip(dims, axes)]
+    dev, psi, Gd, vd, kd = _gmat_dev(psi0s, G, v, ks, ns, copy=True)
+    B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
+    snap = torch.empty((B, nsnap, max(ns, 1)) + dims, dtype=torch.complex128, device=dev)
+    _gmat_call("rk4", dev, psi, ns, Gd, vd, kd, dims, float(dt), nsnap * int(nout), int(nout),
+               snap.data_ptr() if nsnap else None)
+    if ns:
+        return psi.movedim(1, -1).contiguous(), snap.movedim(2, -1).contiguous()
+    return psi[:, 0], snap[:, :, 0]
 
 
 def _like_input(out, psi):
@@ -1143,7 +1157,7 @@ def KEO(psi, kx, ky, G):
     the other axis cancels: one line transform pair per derivative).  G [nx, ny, 2, 2] real, all four entries read.
     Extensions: psi may carry a leading batch axis [B, nx, ny]; a tensor in gives a tensor out on the same device (a
     device tensor stays on the device, a host tensor comes back to the host)."""
-    return _like_input(_gmat_apply(psi, kx, ky, None, G), psi)
+    return _like_input(_gmat_apply(psi, (kx, ky), None, G), psi)
 
 
 def PEO(psi, v):
@@ -1155,7 +1169,7 @@ def hpsi(psi, kx, ky, v, G):
     """wpd.py:1935-1940: -1j (K psi + v psi), one library call for K psi + v psi; v real or complex.
     Extension: v [nx, ny, ns, ns] (any complex matrix per point) with psi [nx, ny, ns] or [B, nx, ny, ns] is the
     coupled-surface operator, -1j (K psi_a + sum_b v_ab psi_b)."""
-    return _like_input(-1j * _gmat_apply(psi, kx, ky, v, G), psi)
+    return _like_input(-1j * _gmat_apply(psi, (kx, ky), v, G), psi)
 
 
 def curvilinear_run(x, y, psi0s, v, G, dt, nt, nout=1):
@@ -1167,34 +1181,7 @@ def curvilinear_run(x, y, psi0s, v, G, dt, nt, nout=1):
     Coupled surfaces: v [nx, ny, ns, ns] with psi0s [B, nx, ny, ns] (or one, [nx, ny, ns]) integrates
     i dpsi_a/dt = K psi_a + sum_b v_ab psi_b (qd_wp2_gmat_ms_rk4) and returns ([B, nx, ny, ns],
     [B, nt // nout, nx, ny, ns]).  The kernels hold the states as planes; the permutes happen on the device."""
-    if nout < 1 or nt < 0:
-        raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
-    if _is_ms(v):
-        nx, ny, ns, _ = _gmat_check_ms(psi0s, G, v, len(x), len(y))
-        kx = 2. * np.pi * fftfreq(nx, interval(x)) if nx > 1 else np.zeros(1)
-        ky = 2. * np.pi * fftfreq(ny, interval(y)) if ny > 1 else np.zeros(1)
-        dev, psi, Gd, vd, kxd, kyd = _gmat_dev_ms(psi0s, G, v, kx, ky)
-        B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
-        snap = torch.empty((B, nsnap, ns, nx, ny), dtype=torch.complex128, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().qd_wp2_gmat_ms_rk4(psi.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(), kxd.data_ptr(),
-                                                kyd.data_ptr(), nx, ny, float(dt), nsnap * int(nout), int(nout),
-                                                snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
-        _lib.check(rc, "qd_wp2_gmat_ms_rk4")
-        return psi.permute(0, 2, 3, 1).contiguous(), snap.permute(0, 1, 3, 4, 2).contiguous()
-    nx, ny, _ = _gmat_check(psi0s, G, v, len(x), len(y))
-    kx = 2. * np.pi * fftfreq(nx, interval(x)) if nx > 1 else np.zeros(1)
-    ky = 2. * np.pi * fftfreq(ny, interval(y)) if ny > 1 else np.zeros(1)
-    dev, t, Gd, vd, kxd, kyd = _gmat_dev(psi0s, G, v, kx, ky)
-    psi = t.clone()
-    B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
-    snap = torch.empty((B, nsnap, nx, ny), dtype=torch.complex128, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qd_wp2_gmat_rk4(psi.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd), kxd.data_ptr(),
-                                         kyd.data_ptr(), nx, ny, float(dt), nsnap * int(nout), int(nout),
-                                         snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
-    _lib.check(rc, "qd_wp2_gmat_rk4")
-    return psi, snap
+    return _gmat_run((x, y), psi0s, v, G, dt, nt, nout)
 
 
 def adiabatic_2d(x, y, psi0, v, dt, Nt=0, coords='linear', mass=None, G=None):
@@ -1216,7 +1203,10 @@ def adiabatic_2d(x, y, psi0, v, dt, Nt=0, coords='linear', mass=None, G=None):
             "wpd.py:1826); use SPO2(x, y, mass, nstates=1) for split-operator dynamics on one surface")
     if coords != 'curvilinear':
         raise ValueError(f"coords = {coords!r}; adiabatic_2d knows 'curvilinear' (and refuses 'linear')")
-    _, _, batched = _gmat_check(psi0, G, v, len(x), len(y))
+    dims, ns, batched = _gmat_check(psi0, G, v, (len(x), len(y)))
+    if ns:
+        raise ValueError(f"v must be {dims} for psi {_shape_of(psi0)}; got {_shape_of(v)} (coupled surfaces: "
+                         "curvilinear_run)")
     psi, _ = curvilinear_run(x, y, psi0, v, G, dt, int(Nt), 1)
     return _like_input(psi if batched else psi[0], psi0)
 
@@ -1224,109 +1214,17 @@ def adiabatic_2d(x, y, psi0, v, dt, Nt=0, coords='linear', mass=None, G=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # Three curvilinear coordinates (extension): the 3 x 3 G-matrix operator and its RK4 propagation
 
-def _shape_of(a):
-    return tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
-
-
-def _gmat_k(n, axis):
-    """k = 2 pi fftfreq(n, d) of an axis of n points, zeros(1) for an axis of length 1."""
-    return 2. * np.pi * fftfreq(n, interval(axis)) if n > 1 else np.zeros(1)
-
-
-def _gmat3_check_G(G, nx, ny, nz, what):
-    if G is None:
-        raise ValueError("curvilinear coordinates need the metric G [nx, ny, nz, 3, 3]")
-    if _shape_of(G) != (nx, ny, nz, 3, 3):
-        raise ValueError(f"G must be {(nx, ny, nz, 3, 3)} for {what}; got {_shape_of(G)}")
-    if _is_complex_nonzero(G):
-        raise ValueError("G must be real: the kernels read a float64 metric (a complex G is not supported)")
-
-
-def _gmat3_check(psi, G, v, nk):
-    """Shape and type checks of a 3-D curvilinear call, before any device call for ndarray and host-tensor operands.
-    v [nx, ny, nz] (or None) takes psi [nx, ny, nz] or a batch [B, nx, ny, nz]; v [nx, ny, nz, ns, ns] takes
-    psi [nx, ny, nz, ns] or [B, nx, ny, nz, ns].  Returns (dims, ns, batched), ns = 0 on a single surface."""
-    shape = _shape_of(psi)
-    vshape = None if v is None else _shape_of(v)
-    if vshape is not None and len(vshape) == 5:
-        want = "v [nx, ny, nz, ns, ns] needs psi [nx, ny, nz, ns] or a batch [B, nx, ny, nz, ns]"
-        if len(shape) not in (4, 5):
-            raise ValueError(f"{want}; got psi {shape}")
-        dims, ns = tuple(int(n) for n in shape[-4:-1]), int(vshape[-1])
-        if vshape != dims + (ns, ns) or ns < 1:
-            raise ValueError(f"v must be [nx, ny, nz, ns, ns] = {dims} + (ns, ns) for psi {shape}; got {vshape}")
-        if int(shape[-1]) != ns:
-            raise ValueError(f"{want}: v {vshape} has ns = {ns}; got psi {shape}")
-        batched = len(shape) == 5
-    else:
-        if len(shape) not in (3, 4):
-            raise ValueError(f"psi must be [nx, ny, nz] or a batch [B, nx, ny, nz]; got {shape}")
-        dims, ns, batched = tuple(int(n) for n in shape[-3:]), 0, len(shape) == 4
-        if vshape is not None and vshape != dims:
-            raise ValueError(f"v must be {dims} (or [nx, ny, nz, ns, ns]) for psi {shape}; got {vshape}")
-    _gmat3_check_G(G, *dims, f"psi {shape}")
-    if tuple(nk) != dims:
-        raise ValueError(f"kx, ky, kz have lengths {tuple(nk)}; psi {shape} needs {dims}")
-    return dims, ns, batched
-
-
-def _gmat3_dev(psi, G, v, ks, ns):
-    """Device operands in the kernels' layout: psi [B, max(ns, 1), nx, ny, nz] (always a copy), G float64,
-    V [ns, ns, nx, ny, nz] or v [nx, ny, nz] complex128 or None, and the three k vectors float64."""
-    dev = psi.device if isinstance(psi, torch.Tensor) and psi.device.type == "cuda" else default_device()
-    _lib.ensure_device(dev)
-    t = psi.to(device=dev, dtype=torch.complex128) if isinstance(psi, torch.Tensor) else _dev_c128(psi, dev)
-    if t.dim() == (4 if ns else 3):
-        t = t[None]
-    t = t.permute(0, 4, 1, 2, 3) if ns else t[:, None]
-    t = t.clone(memory_format=torch.contiguous_format)
-    if isinstance(G, torch.Tensor):
-        Gd = (G.real if G.is_complex() else G).to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        Gd = _dev_f64(np.real(G), dev)
-    vd = None
-    if v is not None:
-        vd = v.to(device=dev, dtype=torch.complex128) if isinstance(v, torch.Tensor) else _dev_c128(v, dev)
-        vd = (vd.permute(3, 4, 0, 1, 2) if ns else vd).contiguous()
-    f64 = lambda k: k.to(device=dev, dtype=torch.float64).contiguous() if isinstance(k, torch.Tensor) \
-        else _dev_f64(k, dev)
-    return dev, t, Gd, vd, [f64(k) for k in ks]
-
-
-def _gmat3_apply(psi, ks, v, G):
-    """(K + v) psi on the device (qd_wp3_gmat_apply, or qd_wp3_gmat_ms_apply for v [nx, ny, nz, ns, ns]); returns a
-    device tensor shaped like psi."""
-    dims, ns, batched = _gmat3_check(psi, G, v, [len(k) for k in ks])
-    dev, t, Gd, vd, kd = _gmat3_dev(psi, G, v, ks, ns)
-    out = torch.empty_like(t)
-    B = int(t.shape[0])
-    with torch.cuda.device(dev):
-        if ns:
-            name = "qd_wp3_gmat_ms_apply"
-            rc = _lib.load().qd_wp3_gmat_ms_apply(t.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(),
-                                                  *(k.data_ptr() for k in kd), *dims, out.data_ptr(),
-                                                  _lib.stream_ptr(dev))
-        else:
-            name = "qd_wp3_gmat_apply"
-            rc = _lib.load().qd_wp3_gmat_apply(t.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd),
-                                               *(k.data_ptr() for k in kd), *dims, out.data_ptr(),
-                                               _lib.stream_ptr(dev))
-    _lib.check(rc, name)
-    out = out.permute(0, 2, 3, 4, 1).contiguous() if ns else out[:, 0]
-    return out if batched else out[0]
-
-
 def KEO3(psi, kx, ky, kz, G):
     """Extension: K psi = 1/2 sum_rs p_r G_rs p_s psi in three curvilinear coordinates, p_a psi = IFFT_a(k_a FFT_a psi),
     G [nx, ny, nz, 3, 3] real with all nine entries read.  psi [nx, ny, nz] or a batch [B, nx, ny, nz]; ndarray in
     gives ndarray out, a tensor comes back on its own device, as KEO."""
-    return _like_input(_gmat3_apply(psi, (kx, ky, kz), None, G), psi)
+    return _like_input(_gmat_apply(psi, (kx, ky, kz), None, G), psi)
 
 
 def hpsi3(psi, kx, ky, kz, v, G):
     """Extension: -1j (K psi + v psi) with KEO3's K; v [nx, ny, nz] real or complex.  v [nx, ny, nz, ns, ns] with
     psi [nx, ny, nz, ns] or [B, nx, ny, nz, ns] is the coupled-surface operator, -1j (K psi_a + sum_b v_ab psi_b)."""
-    return _like_input(-1j * _gmat3_apply(psi, (kx, ky, kz), v, G), psi)
+    return _like_input(-1j * _gmat_apply(psi, (kx, ky, kz), v, G), psi)
 
 
 def curvilinear_run3(x, y, z, psi0s, v, G, dt, nt, nout=1):
@@ -1334,24 +1232,4 @@ def curvilinear_run3(x, y, z, psi0s, v, G, dt, nt, nout=1):
     Runs (nt // nout) nout RK4 steps of B wavepackets psi0s [B, nx, ny, nz] (or one) on one potential and metric
     G [nx, ny, nz, 3, 3]; returns (final states [B, nx, ny, nz], snapshots [B, nt // nout, nx, ny, nz]) as device
     tensors, with a trailing state axis on coupled surfaces.  psi0s is not modified."""
-    if nout < 1 or nt < 0:
-        raise ValueError(f"nt = {nt} must be >= 0 and nout = {nout} >= 1")
-    dims, ns, _ = _gmat3_check(psi0s, G, v, (len(x), len(y), len(z)))
-    ks = [_gmat_k(n, a) for n, a in zip(dims, (x, y, z))]
-    dev, psi, Gd, vd, kd = _gmat3_dev(psi0s, G, v, ks, ns)
-    B, nsnap = int(psi.shape[0]), int(nt) // int(nout)
-    snap = torch.empty((B, nsnap, max(ns, 1)) + dims, dtype=torch.complex128, device=dev)
-    tail = (float(dt), nsnap * int(nout), int(nout), snap.data_ptr() if nsnap else None, _lib.stream_ptr(dev))
-    with torch.cuda.device(dev):
-        if ns:
-            name = "qd_wp3_gmat_ms_rk4"
-            rc = _lib.load().qd_wp3_gmat_ms_rk4(psi.data_ptr(), B, ns, Gd.data_ptr(), vd.data_ptr(),
-                                                *(k.data_ptr() for k in kd), *dims, *tail)
-        else:
-            name = "qd_wp3_gmat_rk4"
-            rc = _lib.load().qd_wp3_gmat_rk4(psi.data_ptr(), B, Gd.data_ptr(), _lib.ptr(vd),
-                                             *(k.data_ptr() for k in kd), *dims, *tail)
-    _lib.check(rc, name)
-    if ns:
-        return psi.permute(0, 2, 3, 4, 1).contiguous(), snap.permute(0, 1, 3, 4, 5, 2).contiguous()
-    return psi[:, 0], snap[:, :, 0]
+    return _gmat_run((x, y, z), psi0s, v, G, dt, nt, nout)
