@@ -8,7 +8,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
-#include <type_traits>
+
+#include "typed_dispatch.hpp"
 
 namespace qd {
 
@@ -164,16 +165,7 @@ inline bool spo1d_plan(int nx, int B, Pass* p) {
   return pow2_in_range(nx);
 }
 
-// ---------------------------------------------------------------- typed dispatch
-// f(std::integral_constant<int, V>{}) for the V of the list that equals v; false when v is not in the list or f
-// returns false (a miss is the caller's internal error, never a silent no-op).
-template <int... Vs, typename F>
-bool dispatch_int(int v, F&& f) {
-  return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
-}
-template <int V>
-using int_c = std::integral_constant<int, V>;
-
+// ---------------------------------------------------------------- typed dispatch (dispatch_int: typed_dispatch.hpp)
 // A 3D column tile has colC ns == midC in {8, 16} lines on nx <= 64, and midC's nx (nz ns / midC) >= 1024 blocks with
 // nz <= 256 need nx >= 4 colC.
 constexpr bool col_tile_ok(int L, int C, int NS) { return (C * NS == 8 || C * NS == 16) && L <= 64 && L >= 4 * C; }

@@ -307,6 +307,18 @@ BANDS_MAX = 256   # one workgroup per CU at most (the bands must be co-resident)
 KRYLOV_MIN_DIM = 1024
 
 
+# The two shape rules of csrc/deom_plan.hpp that decide before any device call (tests/test_deom_plan_host.py holds
+# them against the plans).
+def ado_major_ok(ns, K):
+    """The ADO-major layout needs the lane-group kernel (deom_stage_plan)."""
+    return ns * ns <= 64 and K <= 8
+
+
+def banded_ok(ns, K):
+    """Shapes qd_deom_rk4_banded takes (deom_band_plan); band sizes are checked once the bands exist."""
+    return 2 <= ns <= 4 and K <= 8
+
+
 class _BandTables:
     """Device copies of the tier-band partition (deom_shard.make_plans) in qd_deom_rk4_banded's layout."""
 
@@ -444,7 +456,7 @@ class DEOMSolver:
         if self.layout not in (None, "ado_major", "element_major"):
             raise ValueError(f"DEOMSolver.layout must be None, 'ado_major' or 'element_major', got {self.layout!r}")
         want_am = B >= 16 if self.layout is None else self.layout == "ado_major"
-        ado_major = want_am and ns * ns <= 64 and K <= 8
+        ado_major = want_am and ado_major_ok(ns, K)
         if ado_major:
             ados = torch.zeros((nmax, B, ns, ns), dtype=torch.complex128, device=dev)
             ados[0] = c128(rho0)
@@ -537,7 +549,7 @@ class DEOMSolver:
         if self.banded is False:
             return None
         ns, K, nmax = self.nsys, self.nind, self.nmax
-        if not (2 <= ns <= 4) or K > 8:
+        if not banded_ok(ns, K):
             return None
         G = 4 if ns == 2 else 16
         per, fat = (24, 80) if G == 4 else (8, 20)
