@@ -855,6 +855,92 @@ int qd_photon_echo(const qd_c128* E, const qd_c128* dip, const double* gamma,
                    int n1, const double* probe, int n3, double t2, qd_c128* S,
                    void* stream);
 
+/*
+ * Sum-over-states signals of pyqed/signal/sos.py in factorised form.  With the
+ * fixed-delay factor of a third-order pathway summed first, every pathway is
+ *   S(i, j) = sum_p fx(i, p) * sum_q W[p][q] * fy(j, p, q)
+ * with poles z = (E_u - E_v) - i ((gamma_u + gamma_v) / 2 + gammaD_uv).
+ *
+ * qd_sos_polesum evaluates that sum.  zx [P], zy [P][Q], W [P][Q] complex;
+ * x [n0], y [n1] real grids; S(i, j) is written at S[i * stride_i + j * stride_j]
+ * (every element, never through an atomic; two calls give identical bits).
+ * Factor kinds:
+ *   xkind QD_SOS_POLE   fx = 1 / (x_i - zx[p])
+ *         QD_SOS_UNITY  fx = 1                       (zx, x may be NULL)
+ *         QD_SOS_DIAG   fx = 1 / (y_j - zx[p]): the x factor taken at y_j, the
+ *                       same value in every row i    (x may be NULL)
+ *   ykind QD_SOS_POLE   fy = 1 / (y_j - zy[p][q])
+ *         QD_SOS_UNITY  fy = 1                       (zy may be NULL; y too
+ *                       unless xkind is QD_SOS_DIAG)
+ * accumulate != 0 adds to S.  P == 0 or Q == 0 writes zeros (leaves S as it was
+ * under accumulate).  The strides must address n0 * n1 distinct elements:
+ * (stride_i, stride_j) = (n1, 1) or (1, n0), or larger row pitches of either.
+ * Work: P Q n1 for the inner sums (one reciprocal per (p, q, j)), then P per
+ * grid point.
+ */
+#define QD_SOS_POLE 0
+#define QD_SOS_UNITY 1
+#define QD_SOS_DIAG 2
+int qd_sos_polesum(const qd_c128* zx, const qd_c128* zy, const qd_c128* W, int P,
+                   int Q, const double* x, int n0, const double* y, int n1,
+                   int xkind, int ykind, qd_c128* S, long stride_i,
+                   long stride_j, int accumulate, void* stream);
+
+/*
+ * One third-order pathway of sos.py on two grids wa [na], wb [nb] (in the
+ * reference's argument order) at one delay: builds zx, zy and W on the device
+ * and runs qd_sos_polesum.  E [N] (complex allowed), dip [N][N], gamma [N];
+ * dephasing: pure-dephasing rate added to every off-diagonal linewidth (poles
+ * and delay factor alike; 0 for the reference's GSB / SE / ESA / DQC); g/e/f
+ * index lists (int32, an empty list may be NULL).  The initial state is 0.
+ *   pathway              wa      wb      delay  S
+ *   QD_SOS_GSB/SE/ESA    omega1  omega3  tau2   [nb][na]  (sos.py:624, :731, :498)
+ *   QD_SOS_SE_T3/ESA_T3  omega1  omega2  t3     [nb][na]  (_SE :788, _ESA :560)
+ *   QD_SOS_DQC_R1_T3     omega1  omega2  tau3   [na][nb]  (DQC_R1 :1054; both
+ *                        Green's functions are taken at omega2, as the reference)
+ *   QD_SOS_DQC_R1_T1     omega2  omega3  tau1   [na][nb]
+ *   QD_SOS_DQC_R2_T3     omega1  omega2  tau3   [na][nb]  (DQC_R2 :1147)
+ *   QD_SOS_DQC_R2_T1     omega2  omega3  tau1   [na][nb]  (no -i on the delay factor)
+ *   QD_SOS_CARS          shift   omega1  -      [na][nb]  (cars :1392): all states
+ *                        1 .. N-1, a != b; the Lorentzian in the shift and the omega1
+ *                        pole take the linewidths above, so gamma = 0 and dephasing =
+ *                        the reference's scalar gamma reproduce it; the index lists
+ *                        and the delay are not read.
+ * accumulate != 0 adds the pathway to S.
+ */
+#define QD_SOS_GSB 0
+#define QD_SOS_SE 1
+#define QD_SOS_ESA 2
+#define QD_SOS_SE_T3 3
+#define QD_SOS_ESA_T3 4
+#define QD_SOS_DQC_R1_T3 5
+#define QD_SOS_DQC_R1_T1 6
+#define QD_SOS_DQC_R2_T3 7
+#define QD_SOS_DQC_R2_T1 8
+#define QD_SOS_CARS 9
+#define QD_SOS_NPATHWAYS 10
+int qd_sos_pathway(int pathway, const qd_c128* E, const qd_c128* dip,
+                   const double* gamma, int N, double dephasing,
+                   const int32_t* g_idx, int ng, const int32_t* e_idx, int ne,
+                   const int32_t* f_idx, int nf, double delay, const double* wa,
+                   int na, const double* wb, int nb, qd_c128* S, int accumulate,
+                   void* stream);
+
+/*
+ * Two-photon absorption with classical light (sos.py TPA :349, TPA2D :380,
+ * TPA2D_time_order :408), real E [N]:
+ *   signal[i][j] = sum_f L(wp_i - E_f + E_0; gamma_f) *
+ *     | sum_m d_fm d_m0 ( 1 / (w1_j - (E_m - E_0) + i gamma_m)
+ *                       + s / (wp_i - w1_j - (E_m - E_0) + i gamma_m) ) |^2
+ * L(x; g) = g / (pi (g^2 + x^2)); m over e_idx, f over f_idx; second_order = s
+ * (1: both time orders, 0: TPA2D_time_order).  w1 == NULL: the degenerate scan
+ * w1 = wp_i / 2 with n1 = 1 (TPA).  signal [np][n1] float64.
+ */
+int qd_sos_tpa(const double* E, const qd_c128* dip, const double* gamma, int N,
+               const int32_t* e_idx, int ne, const int32_t* f_idx, int nf,
+               const double* wp, int np, const double* w1, int n1,
+               int second_order, double* signal, void* stream);
+
 /* ------------------------------------------------------------ FFT -------- */
 /*
  * In-place FFT (inverse != 0: unnormalised inverse) along the middle axis of a

@@ -132,6 +132,13 @@ SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "qd_photon_echo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    "qd_sos_polesum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                               c_int, c_void_p, c_long, c_long, c_int, c_void_p]),
+    "qd_sos_pathway": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_void_p, c_int,
+                               c_void_p, c_int, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                               c_void_p]),
+    "qd_sos_tpa": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                           c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "qd_fft_axis": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_double, c_void_p]),
     "qd_dft2": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double,
                         c_void_p, c_void_p]),

@@ -356,7 +356,8 @@ class SESolver:
 
 
 class Mol:
-    """Subset of pyqed.mol.Mol (mol.py:184-957) on the hot path: container, run, photon_echo."""
+    """Subset of pyqed.mol.Mol (mol.py:184-957) on the hot path: container, run, and the sum-over-states signals
+    (photon_echo / PE, PE2, absorption, cars) with the setters of their decay and dephasing rates."""
 
     def __init__(self, H, edip=None, lowering=None, edip_rms=None, gamma=None):
         self.H = H
@@ -425,3 +426,41 @@ class Mol:
         """mol.py:804-829 -> sos.photon_echo (GPU)."""
         from . import sos
         return sos.photon_echo(self, pump=pump, probe=probe, t2=t2, **kwargs)
+
+    def PE(self, pump, probe, t2=0.0, **kwargs):
+        """mol.py:797-802: alias for photon_echo."""
+        return self.photon_echo(pump, probe, t2=t2, **kwargs)
+
+    def PE2(self, omega1, omega2, t3=0.0, **kwargs):
+        """mol.py:831-855 -> sos.photon_echo_t3 (GPU): the echo on (omega1, omega2) at detection time t3."""
+        from . import sos
+        return sos.photon_echo_t3(self, omega1=omega1, omega2=omega2, t3=t3, **kwargs)
+
+    def absorption(self, omegas, method='sos', **kwargs):
+        """mol.py:766-795 -> sos.absorption (GPU); the array alone is returned, nothing plots."""
+        if method == 'sos':
+            from . import sos
+            return sos.absorption(self, omegas, **kwargs)
+        elif method == 'tcf':
+            raise NotImplementedError('The method {} has not been implemented. \
+                              Try "sos"'.format(method))
+
+    def cars(self, shift, omega1, t2=0., plt_signal=False, fname=None):
+        """mol.py:866-888 -> sos.cars (GPU) with edip_rms; plt_signal is accepted and ignored."""
+        from . import sos
+        return sos.cars(self.eigvals(), self.edip_rms, shift, omega1, t2=t2)
+
+    def set_decay_for_all(self, gamma):
+        """mol.py:363-379: one decay rate for every excited state, 0 for the ground state."""
+        self.gamma = [gamma] * self.nstates
+        self.gamma[0] = 0
+        return
+
+    def set_dephasing(self, gamma):
+        """mol.py:381-395: the pure dephasing rate of all coherences (read by PE2)."""
+        self.dephasing = gamma
+
+    def set_decay(self, gamma):
+        """mol.py:397-412: the decay rates of the states."""
+        self.gamma = gamma
+        return
