@@ -4,7 +4,9 @@
 // the k index is XOR-ed with row & 15 on the per-lane SOURCE address and again in the fragment read: the 16 lanes of one
 // ds_read_b128 group (rows r0 .. r0 + 15, one k) hit 16 distinct 16-byte slots.  The B tile keeps the [16 k][128] image.
 // Tile t + 1's loads are issued at the top of tile t into the other buffer; the __syncthreads() that ends a tile waits
-// for them (vmcnt(0)).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
+// for them (vmcnt(0)).  A GEMM's last K-tile stages tile 0 of its follower (lookahead), whole or its B half alone; an
+// A tile may instead come from a wave's registers in the same image (cg_dma_a_slot, the hand-overs at the end of this
+// file).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
 //   P1 += ar br ; P2 += ai bi ; P3 += (ar + ai)(br + bi) ;  re = P1 - P2, im = P3 - P1 - P2
 // with P1 / P2 in the tile's re / im registers until cg_dma_finalise.
 // Hermitian X GEMM: X = A r + sum_c B_c W_c (segment 0; segments >= 1, W = C^+ / 2) for k = X + X^+.  Only k on the
@@ -48,6 +50,40 @@ __device__ __forceinline__ const char* cg_uniform(const void* p) {
   return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
 }
 
+// The A-tile image, written once: element (row, k) of a [128][16] K-tile, row = r0 + lr with r0 the row's 16-tile and
+// lr = row & 15, sits at 16-byte slot row * 16 + (k ^ lr).  Its three users are the DMA source address (slot (row, s)
+// is loaded from column cg_dma_a_kslot(lr, s): the XOR is its own inverse), the fragment read of cg_dma_ksteps, and a
+// wave that writes an accumulator tile into the image from registers (cg_dma_a_tile_write).
+constexpr int cg_dma_a_kslot(int lr, int k) { return k ^ lr; }
+constexpr int cg_dma_a_slot(int r0, int lr, int k) { return (r0 + lr) * CG_KT + cg_dma_a_kslot(lr, k); }
+constexpr bool cg_dma_a_slot_bijective() {   // 128 x 16 onto 0 .. 2047, and the source map undoes the slot map
+  bool seen[128 * CG_KT] = {};
+  for (int row = 0; row < 128; ++row)
+    for (int k = 0; k < CG_KT; ++k) {
+      const int s = cg_dma_a_slot(row & ~15, row & 15, k);
+      if (s < 0 || s >= 128 * CG_KT || seen[s]) return false;
+      if (cg_dma_a_kslot(row & 15, cg_dma_a_kslot(row & 15, k)) != k) return false;
+      seen[s] = true;
+    }
+  return true;
+}
+constexpr bool cg_dma_a_slot_conflict_free() {   // the 16 lanes of one ds_read_b128 group (rows r0 .. r0 + 15, one k):
+  for (int r0 = 0; r0 < 128; r0 += 16)           // 16 distinct slots, one in each 16-byte column of the 256-byte bank row
+    for (int k = 0; k < CG_KT; ++k) {
+      unsigned cols = 0;
+      for (int lr = 0; lr < 16; ++lr) {
+        const int s = cg_dma_a_slot(r0, lr, k);
+        for (int l2 = 0; l2 < lr; ++l2)
+          if (cg_dma_a_slot(r0, l2, k) == s) return false;
+        cols |= 1u << (s & 15);
+      }
+      if (cols != 0xffffu) return false;
+    }
+  return true;
+}
+static_assert(cg_dma_a_slot_bijective(), "A-tile image: slots");
+static_assert(cg_dma_a_slot_conflict_free(), "A-tile image: fragment read groups");
+
 // Per-thread part of the staging addresses (bytes) and the wave's first element of each 512-element load round.
 struct CgDmaStage {
   const CgSeg* segs;
@@ -60,7 +96,7 @@ struct CgDmaStage {
     // A: element e = tid + 512 q sits at LDS slot (row e >> 4, k-slot e & 15) and holds A[row][(e & 15) ^ (row & 15)]
     // (row & 15 = (tid >> 4) & 15 for every q);  B: element e -> B[e / 128][e % 128]
     const int row = tid >> 4;
-    offA = (unsigned)(row * lda + ((tid & 15) ^ (row & 15))) * (unsigned)sizeof(c128);
+    offA = (unsigned)(row * lda + cg_dma_a_kslot(row & 15, tid & 15)) * (unsigned)sizeof(c128);
     offB = (unsigned)((tid >> 7) * ldb + (tid & 127)) * (unsigned)sizeof(c128);
     wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
   }
@@ -80,6 +116,15 @@ struct CgDmaStage {
       __builtin_amdgcn_global_load_lds((cg_gvoid*)(gb + (size_t)q * 4 * ldb * sizeof(c128) + offB),
                                        (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
     }
+  }
+  // one half of issue_at: the B tile at depth kt of B alone (4 loads per thread), for a K-tile whose A half reaches LDS
+  // from registers (glf_eig_kernel.hpp)
+  __device__ __forceinline__ void issue_b_at(const c128* B, int kt, CgLds<128>& L, int buf) const {
+    const char* gb = cg_uniform(B + (size_t)kt * ldb);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(gb + (size_t)q * 4 * ldb * sizeof(c128) + offB),
+                                       (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
   }
 };
 
@@ -101,7 +146,7 @@ __device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAc
     double sa[MW];
 #pragma unroll
     for (int mi = 0; mi < MW; ++mi) {
-      a[mi] = L.a[buf][(r0[mi] + lr) * CG_KT + ((kk + lk) ^ lr)];
+      a[mi] = L.a[buf][cg_dma_a_slot(r0[mi], lr, kk + lk)];
       if ((LIVE >> (mi * 4)) & 15u) sa[mi] = a[mi].re + a[mi].im;
     }
 #pragma unroll
@@ -273,22 +318,88 @@ __device__ __forceinline__ void cg_dma_finalise_live(CgAcc3& acc) {
     }
 }
 
+// ---------------------------------------------------------------- hand-overs through LDS (glf_eig_kernel.hpp)
+// The two GEMMs of a stage whose operands are each other's results hand the first K-tiles over in LDS instead of
+// through memory and a cold prologue.  These are cg_dma_block_gemm_stream and the Hermitian segments of
+// cg_dma_herm_x_gemm with the lookahead and the prologue made selectable.  Every tile-end barrier is written as s_waitcnt
+// vmcnt(0) + __syncthreads(): the hand-overs' arguments count on the drain, so it is spelled out instead of left to
+// the fence the compiler puts in front of a barrier with a DMA in flight.
+
+// cg_dma_block_gemm_stream whose follower may take the A half of its tile 0 from registers: nA == nullptr makes the
+// lookahead the B half alone (tile 0 of nB -> L.b[0]) and leaves L.a[0] and, behind the closing barrier, all of
+// buffer 1 to the caller.  L.a[0] was last read at tile T - 2, one barrier before the closing one.
+__device__ __forceinline__ void cg_dma_block_gemm_stream_h(const c128* A, const c128* B, const c128* nA, const c128* nB,
+                                                           bool first, int K, int lda, int ldb, CgLds<128>& L,
+                                                           CgAcc3& acc) {
+  constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
+  const int r0[2] = {wr0, wr0 + 16}, c0[4] = {wc0, wc0 + 16, wc0 + 32, wc0 + 48};
+  cg_dma_zero(acc);
+  const int T = K / CG_KT;
+  const CgDmaStage st(nullptr, T, lda, ldb);
+  if (first) {
+    st.issue_at(A, B, 0, L, 0);
+    __syncthreads();
+  }
+  for (int t = 0; t < T; ++t) {
+    if (t + 1 < T) st.issue_at(A, B, (t + 1) * CG_KT, L, (t + 1) & 1);
+    else if (nA) st.issue_at(nA, nB, 0, L, 0);
+    else st.issue_b_at(nB, 0, L, 0);
+    cg_sched_fence();
+    cg_dma_ksteps<0u, 0, NQ>(L, t & 1, acc, r0, c0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  cg_dma_finalise(acc);
+}
+
+// Accumulator tile (mi, nj) of the CgCfg<128> layout (finalised: re / im) written into the A-tile image of buffer buf
+// as the 16 columns [16 kt0 .. 16 kt0 + 15] of the rows the wave owns: the MFMA result map (register e of lane l =
+// element ((l >> 4) + 4 e, l & 15)) through cg_dma_a_slot.  One ds_write_b128 per register; the 64 lanes of one cover
+// four whole 256-byte rows of the image.
+__device__ __forceinline__ void cg_dma_a_tile_write(const CgAcc3& acc, int mi, int nj, int row0 /* % 16 == 0 */, int lane,
+                                                    CgLds<128>& L, int buf) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    L.a[buf][cg_dma_a_slot(row0, (lane >> 4) + 4 * e, lane & 15)] = cmk(acc.re[mi][nj][e], acc.im[mi][nj][e]);
+}
+
 // The Hermitian sum D = sum_c B_c W_c on its own (no segment 0, no halving): wave W's part on the tiles on and above the
 // diagonal of the Hermitian tile layout, from a zeroed accumulator over every segment (segs[c] = (B_c, W_c), W_c in
 // full).  The tiles below the diagonal are never touched: with W fixed at compile time they take no registers, so a
-// wave holds at most 5 live tiles.  Called from a per-wave code path (switch on the wave index) by all threads; stages
-// its own tile 0 and ends with a workgroup barrier.  The caller makes the B_c complete and workgroup-visible first, and
-// finishes with cg_dma_finalise_live on the live tiles (after issuing whatever loads its epilogue wants in flight).
+// wave holds at most 5 live tiles.  Called from a per-wave code path (switch on the wave index) by all threads; ends
+// with a workgroup barrier; the caller finishes with cg_dma_finalise_live on the live tiles.  No prologue of its own.
+// two = false: tile 0 sits in buffer 0, staged and waited for by the GEMM before it (an ordinary lookahead).  two = true: tiles 0 AND 1 are the caller's: tile 0 complete in buffer 0
+// behind a barrier, the A half of tile 1 complete in L.a[1] behind the same barrier, the B half of tile 1 in flight to
+// L.b[1] as this wave's own DMA.  Tile 0 then issues nothing and its closing wait and barrier cover that DMA; the
+// stream from memory starts with tile 2, issued at the top of tile 1.
 template <int W>
-__device__ __forceinline__ void cg_dma_herm_d_gemm(const CgSeg* segs, int nseg, int K, int lda, int ldb, CgLds<128>& L,
-                                                   CgAcc3& acc) {
+__device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, int nseg, int K, int lda, int ldb,
+                                                     CgLds<128>& L, CgAcc3& acc, bool two) {
   constexpr unsigned SK = cg_herm_mask(W, true);
+  constexpr int NQ = CG_KT / 4, R0 = 16 * (W >> 1), R1 = 16 * (7 - (W >> 1));
+  const int r0[2] = {R0, R1};
+  const int c0[4] = {16 * cg_herm_ctile(W, 0), 16 * cg_herm_ctile(W, 1), 16 * cg_herm_ctile(W, 2),
+                     16 * cg_herm_ctile(W, 3)};
   cg_dma_zero(acc);
   const int tps = K / CG_KT, T = nseg * tps;
   const CgDmaStage st(segs, tps, lda, ldb);
-  st.issue(0, L, 0);
-  __syncthreads();
-  cg_dma_herm_x_range<W, SK>(0, T, T, st, L, acc);
+  int t = 0;
+  if (two) {   // both buffers named by literals: the fragment reads of buffer 0 do not wait for the DMA into buffer 1
+    cg_sched_fence();
+    cg_dma_ksteps<SK, 0, NQ>(L, 0, acc, r0, c0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    t = 1;
+  }
+  for (; t < T; ++t) {
+    if (t + 1 < T) st.issue(t + 1, L, (t + 1) & 1);
+    cg_sched_fence();
+    cg_dma_ksteps<SK, 0, NQ>(L, t & 1, acc, r0, c0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
 }
 
 }  // namespace qd

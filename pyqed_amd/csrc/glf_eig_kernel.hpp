@@ -4,7 +4,7 @@
 //     d rho~/dt = Lam~ o rho~ + sum_c C~_c rho~ C~_c^+ ,   Lam~_ij = lam_i + conj(lam_j)
 // so the A term is an elementwise multiply in the stage epilogue and only the dissipator is a GEMM.  The dissipator
 // of a Hermitian rho~ is Hermitian on its own: the second GEMM runs on the 36 16 x 16 tiles on and above the diagonal
-// (cg_dma_herm_d_gemm), each upper element's owner writes its mirror as the conjugate, and no X + X^+ pass through
+// (cg_dma_herm_d_gemm_h), each upper element's owner writes its mirror as the conjugate, and no X + X^+ pass through
 // LDS exists.  Per stage (64 + 36) nc tile-GEMMs for the 64 + (64 + 36) nc of glf_batch_kernel.hpp (nc = 1: 9,600
 // against 15,744 3-product MFMAs).  One persistent workgroup per matrix.  Only glf_eig.hip includes this header: next
 // to the kernels of glf.hip it changed the batch kernel's register allocation (3 spilled VGPRs).
@@ -15,6 +15,10 @@
 // Every result is exactly Hermitian with an exactly real diagonal by construction.  RK4 of a linear equation commutes
 // with the fixed change of variables, so in exact arithmetic the back-transformed state is the persistent kernel's;
 // in floating point it differs from it in rounding, scaled by cond(V) (guarded on the host).
+// A phase is one K-tile stream: every GEMM but its first finds its first K-tile in LDS buffer 0, put there under the
+// GEMM before it, and between the Y GEMM and the second GEMM at n_c = 1 the first two K-tiles of Y go from the
+// accumulators into the staging buffers (eig_y_handover) instead of through memory, a drain and a cold prologue.  The
+// hand-overs and the waits and barriers each one rests on are listed in the kernel's phase loop.
 // Register budget: the second GEMM holds at most 5 live tiles (120 accumulator VGPRs); 0 spilled VGPRs, 0 B scratch
 // (tools/isa_diff.py).
 #pragma once
@@ -129,6 +133,35 @@ __device__ __forceinline__ void eig_tail(CgAcc3& A, const c128* r, const c128* b
     }
 }
 
+// Y = M r of an n_c = 1 phase handed to the second GEMM: columns 0 .. 31 are K-tiles 0 and 1 of its A operand and sit,
+// finalised, in the accumulators of the four waves with wc0 == 0 (column tiles nj = 0, 1 of both row tiles).  Those go
+// into L.a[0] and L.a[1] from the registers and never to memory; every other column is stored to Y as before and
+// streamed back from tile 2 on.
+__device__ __forceinline__ void eig_y_handover(const CgAcc3& A, c128* Y, CgLds<128>& L) {
+  constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));   // as in cg_epilogue
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
+  if (wc0 == 0) {
+#pragma unroll
+    for (int mi = 0; mi < MW; ++mi) {
+      cg_dma_a_tile_write(A, mi, 0, wr0 + mi * 16, lane, L, 0);
+      cg_dma_a_tile_write(A, mi, 1, wr0 + mi * 16, lane, L, 1);
+    }
+  }
+#pragma unroll
+  for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int nj = 0; nj < NW; ++nj) {
+        if (nj < 2 && wc0 == 0) continue;
+        const int row = wr0 + mi * 16 + (lane >> 4) + 4 * e, col = wc0 + nj * 16 + (lane & 15);
+        Y[(size_t)row * EIG_NP + col] = cmk(A.re[mi][nj][e], A.im[mi][nj][e]);
+      }
+}
+
 __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p) {
   constexpr int BT = EIG_NP, Np = EIG_NP;
   constexpr size_t NN = (size_t)Np * Np;
@@ -168,11 +201,30 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
 #ifdef QD_PHASE_TIMING
     unsigned long long tkeep[4] = {tacc[0], tacc[1], tacc[2], tacc[3]};
 #endif
-    // One K-tile stream over the first GEMMs Y_c = M_c r: each stages tile 0 of the next one under its last K-tile.
-    // The second GEMM reads every Y_c, so it starts behind the last Y store (drained, then a barrier: one CU,
-    // write-through L1) with a prologue of its own; the last Y GEMM's lookahead has no follower to serve and restages
-    // its own tile 0 into the free buffer, unused.  The segment table is written ahead of the Y GEMMs' barriers; its
-    // last reader in the phase before is separated from these writes by that phase's closing barrier.
+    // One K-tile stream per phase: every GEMM but the phase's first finds its tile 0 in LDS buffer 0, and no barrier,
+    // drain or prologue stands between a GEMM and its follower.  The segment table is written ahead of the Y GEMMs'
+    // barriers; its last reader in the phase before is separated from these writes by that phase's closing barrier.
+    // T = 8 n is even: every GEMM's last K-tile reads buffer 1 and buffer 0 was last read one
+    // barrier earlier.  Every tile-end barrier of the two engines used here is s_waitcnt vmcnt(0) + barrier.
+    // Invariants (keep ALL of these when editing):
+    //  (1) Y_c -> Y_{c+1} (n >= 2): the lookahead of cg_dma_block_gemm_stream, (M_{c+1}, r) tile 0.
+    //  (2) last Y GEMM -> second GEMM, n = 1.  Tiles 0 and 1 of the second GEMM's A operand are columns 0 .. 31 of Y
+    //      and go from the accumulators into L.a[0] and L.a[1] (eig_y_handover); the B halves are DMA: W tile 0 ->
+    //      L.b[0] as the Y GEMM's lookahead, W tile 1 -> L.b[1] behind its closing barrier.
+    //      WAR: L.a[0] and L.b[0] were last read at Y tile 6 and L.a[1], L.b[1] at Y tile 7; the lookahead is issued
+    //      behind tile 6's barrier, the ds_writes and the second DMA behind tile 7's (the closing one).
+    //      RAW: L.b[0]: the closing barrier's vmcnt(0).  L.a[0], L.a[1]: each writer's s_waitcnt lgkmcnt(0), then the
+    //      raw s_barrier below, ahead of tile 0's fragment reads.  That barrier must not be a __syncthreads(): with
+    //      the DMA and the Y stores in flight it would drain both.  L.b[1]: in flight across it; tile 0 reads buffer
+    //      0 only and its closing s_waitcnt vmcnt(0) + barrier retire the DMA ahead of tile 1's reads.
+    //      Y in memory: vmcnt counts stores, so the same tile-0 wait completes every wave's Y stores and the barrier
+    //      makes all of Y (columns 32 .. 127) workgroup-visible (one CU, write-through L1) ahead of the first DMA read
+    //      of it, tile 2, issued at the top of tile 1.  Nothing is issued at the top of tile 0.
+    //  (3) last Y GEMM -> second GEMM, n >= 2: an ordinary lookahead of (Y_0, W_0) tile 0.  Y_0 was stored ahead of
+    //      Y GEMM 1, whose seven drained tile-end barriers precede the first such lookahead; Y_{n-1} is first read at
+    //      tile 8 (n - 1) - 1 of the second GEMM, behind at least seven of its drained barriers.
+    //  (4) nothing between a hand-over and its reader touches the staging buffers: the Y epilogue and eig_tail store
+    //      from registers.
     int tid0 = threadIdx.x;
     asm volatile("" : "+v"(tid0));
     if (tid0 == 0)
@@ -180,23 +232,33 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
         segs[c].A = Y + (size_t)c * NN;
         segs[c].B = Wm + (size_t)c * NN;
       }
+    const bool hand = n == 1;
     for (int c = 0; c < n; ++c) {
       const c128* Mc = M + (size_t)c * NN;
-      cg_dma_block_gemm_stream(Mc, r, c + 1 < n ? Mc + NN : Mc, r, c == 0, Np, Np, Np, L, A);
+      const bool last = c + 1 == n;
+      cg_dma_block_gemm_stream_h(Mc, r, last ? (hand ? nullptr : Y) : Mc + NN, last ? Wm : r, c == 0, Np, Np,
+                                 Np, L, A);
       QD_TMARK(0);
       c128* Yc = Y + (size_t)c * NN;
-      cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
+      if (hand) {
+        eig_y_handover(A, Yc, L);
+        const CgDmaStage st(nullptr, Np / CG_KT, Np, Np);
+        st.issue_b_at(Wm, CG_KT, L, 1);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's ds_writes; NOT vmcnt: see (2)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      } else {
+        cg_epilogue<BT>(A, [&](int row, int col, c128 v) { Yc[(size_t)row * Np + col] = v; });
+      }
       QD_TMARK(1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Y stores are complete
-    __syncthreads();
     {
       int tid = threadIdx.x;
       asm volatile("" : "+v"(tid));   // the per-element index math stays inside the phase
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
       auto tail = [&](auto wc) {
         constexpr int W = decltype(wc)::value;
-        cg_dma_herm_d_gemm<W>(segs, n, Np, Np, Np, L, A);
+        cg_dma_herm_d_gemm_h<W>(segs, n, Np, Np, Np, L, A, hand);
         QD_TMARK(2);
         eig_tail<W>(A, r, rho, rn, lamS, lane, ag, ag, hc);
       };

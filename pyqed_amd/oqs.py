@@ -66,8 +66,9 @@ def _is_hermitian_cached(H: torch.Tensor) -> bool:
 EIG_NP = 128            # the kernel's padded dimension
 EIG_MIN_BATCH = 208     # where the library picks the persistent kernel (glf.hip)
 EIG_MAX_NC = 256        # MAX_NC of the kernels' LDS segment tables
-EIG_MIN_STEPS = 2       # a call's two basis changes cost half a step: a 1-step call ties with the persistent kernel
-                        # (0.614 against 0.612 ms at B = 256), 2 steps 0.978 against 1.140 (profiles/r11/lindblad)
+EIG_MIN_STEPS = 1       # a call's two basis changes cost half a step; with the Y GEMM's hand-over through LDS a 1-step
+                        # call takes 0.582 against the persistent kernel's 0.609 ms at B = 256, 2 steps 0.935 against
+                        # 1.143 (profiles/r12/lindblad/len_sweep.txt)
 # Guards.  A non-normal A has a non-unitary V, and every rounding error of the transformed propagation comes back
 # multiplied by cond_2(V)^2; at an exceptional point A is defective and V singular.  EIG_MAX_COND is the largest
 # cond_2(V) of the damping sweep of tests/test_lindblad_eig_plan_cpu.py (gamma -> 4g in the two-level family embedded
