@@ -3,10 +3,11 @@
 // An LDS-DMA load writes lane-linearly (wave base + lane * 16 B), so the A tile is [128 rows][16 k] without padding and
 // the k index is XOR-ed with row & 15 on the per-lane SOURCE address and again in the fragment read: the 16 lanes of one
 // ds_read_b128 group (rows r0 .. r0 + 15, one k) hit 16 distinct 16-byte slots.  The B tile keeps the [16 k][128] image.
-// Tile t + 1's loads are issued at the top of tile t into the other buffer; the __syncthreads() that ends a tile waits
-// for them (vmcnt(0)).  A GEMM's last K-tile stages tile 0 of its follower (lookahead), whole or its B half alone; an
-// A tile may instead come from a wave's registers in the same image (cg_dma_a_slot, the hand-overs at the end of this
-// file).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
+// Tile t + 1's loads are issued at the top of tile t into the other buffer (the batch kernel's engines) or two at a time
+// under tile t's first four half k-steps (glf_eig_kernel.hpp's engines: CgDmaStageHook); the __syncthreads() that ends
+// a tile waits for them (vmcnt(0)).  A GEMM's last K-tile stages tile 0 of its follower (lookahead), whole or its B half
+// alone; an A tile may instead come from a wave's registers in the same image (cg_dma_a_slot, the hand-overs at the end
+// of this file).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
 //   P1 += ar br ; P2 += ai bi ; P3 += (ar + ai)(br + bi) ;  re = P1 - P2, im = P3 - P1 - P2
 // with P1 / P2 in the tile's re / im registers until cg_dma_finalise.
 // Hermitian X GEMM: X = A r + sum_c B_c W_c (segment 0; segments >= 1, W = C^+ / 2) for k = X + X^+.  Only k on the
@@ -117,6 +118,17 @@ struct CgDmaStage {
                                        (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
     }
   }
+  // piece i (0 .. 7) of a K-tile's eight loads per thread: A round i (i < 4) or B round i - 4 of issue_at, from the tile's
+  // uniform bases ga = A + kt and gb = B + kt ldb (cg_uniform)
+  __device__ __forceinline__ void piece(const char* ga, const char* gb, int i, CgLds<128>& L, int buf) const {
+    const int q = i & 3;
+    if (i >= 4)
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(gb + (size_t)q * 4 * ldb * sizeof(c128) + offB),
+                                       (cg_lvoid*)(&L.b[buf][wbase + CG_WG * q]), 16, 0, 0);
+    else
+      __builtin_amdgcn_global_load_lds((cg_gvoid*)(ga + (size_t)q * 32 * lda * sizeof(c128) + offA),
+                                       (cg_lvoid*)(&L.a[buf][wbase + CG_WG * q]), 16, 0, 0);
+  }
   // one half of issue_at: the B tile at depth kt of B alone (4 loads per thread), for a K-tile whose A half reaches LDS
   // from registers (glf_eig_kernel.hpp)
   __device__ __forceinline__ void issue_b_at(const c128* B, int kt, CgLds<128>& L, int buf) const {
@@ -128,13 +140,92 @@ struct CgDmaStage {
   }
 };
 
+// The hook of cg_dma_ksteps: hook(p) runs at point p = 2 q + h / 2 of the stream (0 .. 7 for a whole K-tile), behind the
+// fragment reads of half k-step (q, h) and ahead of its MFMAs.  The default does nothing and leaves no instruction: the
+// batch kernel's instantiations are the ones they were.
+struct CgNoHook {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+
+// Staging under the k-steps (glf_eig_kernel.hpp's two engines): the eight pieces of the K-tile (ga, gb) -> buffer buf go
+// out two at the points 0 .. 3, the A rounds at points 0 and 1 and the B rounds at 2 and 3, each pair behind a half
+// k-step's fragment reads and under its 12 MFMAs, so that no wave opens a K-tile with eight loads in front of its first
+// fragment.  ga == nullptr: the B half alone (points 2 and 3); gb == nullptr: nothing.  Both tests are uniform
+// branches, and they also keep the loads in basic blocks of their own: hipcc's waitcnt pass puts s_waitcnt vmcnt(0)
+// in front of an LDS read that follows LDS-DMA loads in the SAME block when it cannot tell their buffers apart (a
+// run-time buffer index), which makes the read wait for the whole DMA it was meant to run under.  tools/dma_waits.py
+// finds such waits in the listing; there must be none.
+constexpr int CG_STAGE_PER = 2;   // pieces per point
+struct CgDmaStageHook {
+  const CgDmaStage& st;
+  CgLds<128>& L;
+  const char* ga;
+  const char* gb;
+  int buf;
+  __device__ __forceinline__ void operator()(int p) const {
+    if (p * CG_STAGE_PER >= 8) return;
+    if (!gb) return;
+    if (ga) {
+#pragma unroll
+      for (int i = p * CG_STAGE_PER; i < (p + 1) * CG_STAGE_PER; ++i)
+        if (i < 4) st.piece(ga, gb, i, L, buf);
+    }
+#pragma unroll
+    for (int i = p * CG_STAGE_PER; i < (p + 1) * CG_STAGE_PER; ++i)
+      if (i >= 4) st.piece(ga, gb, i, L, buf);
+  }
+};
+
+// QD_PHASE_TIMING builds: the two engines of glf_eig_kernel.hpp stamp each K-tile per wave with the shader clock and no
+// barrier in front: tk[o] the head (tile-end barrier released -> the first fragment reads and whatever the hook issues at
+// point 0 are out), tk[o + 1] the k-steps (-> the last MFMA is issued), tk[o + 2] the tile-end wait and barrier.
+#ifdef QD_PHASE_TIMING
+#define CG_KSTAMP_PARAM , unsigned long long (&tk)[6], int tko
+#define CG_KSTAMP_ARG(a, o) , a, o
+#define CG_KSTAMP_TOP unsigned long long ks0_ = clock64(), ks1_ = ks0_;
+#define CG_KSTAMP_END                  \
+  cg_sched_fence();                    \
+  const unsigned long long ks2_ = clock64(); \
+  cg_sched_fence();
+#define CG_KSTAMP_BAR                              \
+  {                                                \
+    const unsigned long long ks3_ = clock64();     \
+    tk[tko] += ks1_ - ks0_;                        \
+    tk[tko + 1] += ks2_ - ks1_;                    \
+    tk[tko + 2] += ks3_ - ks2_;                    \
+    ks0_ = ks3_;                                   \
+  }
+// hook H, then the clock at point 0
+template <class H>
+struct CgStampHook {
+  const H& h;
+  unsigned long long& at;
+  __device__ __forceinline__ void operator()(int p) const {
+    h(p);
+    if (p == 0) {
+      cg_sched_fence();
+      at = clock64();
+      cg_sched_fence();
+    }
+  }
+};
+#define CG_KSTAMP_HOOK(h) CgStampHook<decltype(h)>{h, ks1_}
+#else
+#define CG_KSTAMP_PARAM
+#define CG_KSTAMP_ARG(a, o)
+#define CG_KSTAMP_TOP
+#define CG_KSTAMP_END
+#define CG_KSTAMP_BAR
+#define CG_KSTAMP_HOOK(h) h
+#endif
+
 // k-steps [Q0, Q1) of one K-tile for a wave with row tiles at r0[], column tiles at c0[] and the tiles SK skipped (the
 // Hermitian segments' tiles below the diagonal; 0 elsewhere).  The B fragments are read and consumed two at a time and
 // each operand sum is formed where its fragment is read: the third accumulator set takes the registers that a
 // 4-product k-step spends on holding all four B fragments at once.
-template <unsigned SK, int Q0, int Q1>
+template <unsigned SK, int Q0, int Q1, class Hook = CgNoHook>
 __device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAcc3& acc, const int (&r0)[2],
-                                              const int (&c0)[4]) {
+                                              const int (&c0)[4], const Hook& hook = Hook()) {
   constexpr int BT = 128, MW = 2, NW = 4;
   constexpr unsigned LIVE = 0xffu & ~SK;   // the tiles this range computes
   const int lane = threadIdx.x & 63;
@@ -161,6 +252,7 @@ __device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAc
           sb[j] = b[j].re + b[j].im;
         }
       }
+      hook(2 * q + h / 2);
 #pragma unroll
       for (int mi = 0; mi < MW; ++mi)
 #pragma unroll
@@ -324,13 +416,18 @@ __device__ __forceinline__ void cg_dma_finalise_live(CgAcc3& acc) {
 // cg_dma_herm_x_gemm with the lookahead and the prologue made selectable.  Every tile-end barrier is written as s_waitcnt
 // vmcnt(0) + __syncthreads(): the hand-overs' arguments count on the drain, so it is spelled out instead of left to
 // the fence the compiler puts in front of a barrier with a DMA in flight.
+// Both engines stage the next K-tile from inside the k-steps (CgDmaStageHook: two pieces at each of the points 0 .. 3)
+// instead of ahead of them.  Issuing later is safe by construction: the target buffer has been free since the tile-end
+// barrier before (WAR), and the issuing wave's tile-end s_waitcnt vmcnt(0) followed by the barrier still covers every
+// piece ahead of any wave's read of it (RAW): nothing else orders another wave's ds_read behind an LDS-DMA load.  The
+// last piece goes out under k-step 1, with half the tile's MFMAs (two k-steps of both waves of the SIMD) behind it.
 
 // cg_dma_block_gemm_stream whose follower may take the A half of its tile 0 from registers: nA == nullptr makes the
 // lookahead the B half alone (tile 0 of nB -> L.b[0]) and leaves L.a[0] and, behind the closing barrier, all of
 // buffer 1 to the caller.  L.a[0] was last read at tile T - 2, one barrier before the closing one.
 __device__ __forceinline__ void cg_dma_block_gemm_stream_h(const c128* A, const c128* B, const c128* nA, const c128* nB,
                                                            bool first, int K, int lda, int ldb, CgLds<128>& L,
-                                                           CgAcc3& acc) {
+                                                           CgAcc3& acc CG_KSTAMP_PARAM) {
   constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wr0 = (wave / WC) * (MW * 16), wc0 = (wave % WC) * (NW * 16);
@@ -342,14 +439,19 @@ __device__ __forceinline__ void cg_dma_block_gemm_stream_h(const c128* A, const 
     st.issue_at(A, B, 0, L, 0);
     __syncthreads();
   }
+  CG_KSTAMP_TOP
   for (int t = 0; t < T; ++t) {
-    if (t + 1 < T) st.issue_at(A, B, (t + 1) * CG_KT, L, (t + 1) & 1);
-    else if (nA) st.issue_at(nA, nB, 0, L, 0);
-    else st.issue_b_at(nB, 0, L, 0);
+    // the tile staged under this one: tile t + 1, or at the last tile the follower's tile 0, whole or its B half alone
+    const bool more = t + 1 < T;
+    const char* ga = more ? cg_uniform(A + (t + 1) * CG_KT) : nA ? cg_uniform(nA) : nullptr;
+    const char* gb = cg_uniform(more ? B + (size_t)(t + 1) * CG_KT * ldb : nB);
+    const CgDmaStageHook hook{st, L, ga, gb, more ? (t + 1) & 1 : 0};
     cg_sched_fence();
-    cg_dma_ksteps<0u, 0, NQ>(L, t & 1, acc, r0, c0);
+    cg_dma_ksteps<0u, 0, NQ>(L, t & 1, acc, r0, c0, CG_KSTAMP_HOOK(hook));
+    CG_KSTAMP_END
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    CG_KSTAMP_BAR
   }
   cg_dma_finalise(acc);
 }
@@ -372,11 +474,11 @@ __device__ __forceinline__ void cg_dma_a_tile_write(const CgAcc3& acc, int mi, i
 // with a workgroup barrier; the caller finishes with cg_dma_finalise_live on the live tiles.  No prologue of its own.
 // two = false: tile 0 sits in buffer 0, staged and waited for by the GEMM before it (an ordinary lookahead).  two = true: tiles 0 AND 1 are the caller's: tile 0 complete in buffer 0
 // behind a barrier, the A half of tile 1 complete in L.a[1] behind the same barrier, the B half of tile 1 in flight to
-// L.b[1] as this wave's own DMA.  Tile 0 then issues nothing and its closing wait and barrier cover that DMA; the
-// stream from memory starts with tile 2, issued at the top of tile 1.
+// L.b[1] as this wave's own DMA.  Tile 0 then issues nothing (no hook) and its closing wait and barrier cover that DMA;
+// the stream from memory starts with tile 2, issued inside tile 1; the last tile's hook issues nothing.
 template <int W>
 __device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, int nseg, int K, int lda, int ldb,
-                                                     CgLds<128>& L, CgAcc3& acc, bool two) {
+                                                     CgLds<128>& L, CgAcc3& acc, bool two CG_KSTAMP_PARAM) {
   constexpr unsigned SK = cg_herm_mask(W, true);
   constexpr int NQ = CG_KT / 4, R0 = 16 * (W >> 1), R1 = 16 * (7 - (W >> 1));
   const int r0[2] = {R0, R1};
@@ -386,19 +488,32 @@ __device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, int nseg
   const int tps = K / CG_KT, T = nseg * tps;
   const CgDmaStage st(segs, tps, lda, ldb);
   int t = 0;
+  CG_KSTAMP_TOP
   if (two) {   // both buffers named by literals: the fragment reads of buffer 0 do not wait for the DMA into buffer 1
     cg_sched_fence();
-    cg_dma_ksteps<SK, 0, NQ>(L, 0, acc, r0, c0);
+    const CgNoHook none;
+    cg_dma_ksteps<SK, 0, NQ>(L, 0, acc, r0, c0, CG_KSTAMP_HOOK(none));
+    CG_KSTAMP_END
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    CG_KSTAMP_BAR
     t = 1;
   }
   for (; t < T; ++t) {
-    if (t + 1 < T) st.issue(t + 1, L, (t + 1) & 1);
+    const char *ga = nullptr, *gb = nullptr;   // the last tile stages nothing
+    if (t + 1 < T) {
+      const CgSeg sg = segs[(t + 1) / tps];
+      const int kt = ((t + 1) % tps) * CG_KT;
+      ga = cg_uniform(sg.A + kt);
+      gb = cg_uniform(sg.B + (size_t)kt * ldb);
+    }
+    const CgDmaStageHook hook{st, L, ga, gb, (t + 1) & 1};
     cg_sched_fence();
-    cg_dma_ksteps<SK, 0, NQ>(L, t & 1, acc, r0, c0);
+    cg_dma_ksteps<SK, 0, NQ>(L, t & 1, acc, r0, c0, CG_KSTAMP_HOOK(hook));
+    CG_KSTAMP_END
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    CG_KSTAMP_BAR
   }
 }
 

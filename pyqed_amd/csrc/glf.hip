@@ -733,8 +733,8 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   const bool timing = false;
 #endif
   if (timing) {
-    QD_HIP(hipMalloc(&p.tbuf, (size_t)B * 8 * sizeof(unsigned long long)));
-    QD_HIP(hipMemsetAsync(p.tbuf, 0, (size_t)B * 8 * sizeof(unsigned long long), st));
+    QD_HIP(hipMalloc(&p.tbuf, (size_t)B * QD_TSTRIDE * sizeof(unsigned long long)));
+    QD_HIP(hipMemsetAsync(p.tbuf, 0, (size_t)B * QD_TSTRIDE * sizeof(unsigned long long), st));
   }
 
   auto launch_split = [&]() -> int {
@@ -817,7 +817,7 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
     QD_HIP(hipGetLastError());
   }
   if (timing) {
-    std::vector<unsigned long long> t((size_t)B * 8);
+    std::vector<unsigned long long> t((size_t)B * QD_TSTRIDE);
     QD_HIP(hipStreamSynchronize(st));
     QD_HIP(hipMemcpy(t.data(), p.tbuf, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     (void)hipFree(p.tbuf);
@@ -829,13 +829,13 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
                  herm, nsteps);
     for (int q = 0; q < 6; ++q) {
       double s = 0;
-      for (int b = 0; b < B; ++b) s += (double)t[(size_t)b * 8 + q];
+      for (int b = 0; b < B; ++b) s += (double)t[(size_t)b * QD_TSTRIDE + q];
       std::fprintf(stderr, " %s %.2f", names[q], s / B / (khz * 1e-3) / std::max(1, nsteps));
     }
     double cyc = 0, wt = 0;
     for (int b = 0; b < B; ++b) {
-      cyc += (double)t[(size_t)b * 8 + 6];
-      wt += (double)t[(size_t)b * 8 + 7];
+      cyc += (double)t[(size_t)b * QD_TSTRIDE + QD_TCLK];
+      wt += (double)t[(size_t)b * QD_TSTRIDE + QD_TWALL];
     }
     std::fprintf(stderr, " | shader clock %.0f MHz\n", wt > 0 ? cyc / (wt / (khz * 1e3)) / 1e6 : 0.0);
   }

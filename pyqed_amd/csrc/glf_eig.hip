@@ -74,8 +74,8 @@ extern "C" int qd_lindblad_rk4_eig(const qd_c128* lam, const qd_c128* V, const q
   p.dt = dt;
   p.tbuf = nullptr;
 #ifdef QD_PHASE_TIMING
-  QD_HIP(hipMalloc(&p.tbuf, (size_t)B * 8 * sizeof(unsigned long long)));
-  QD_HIP(hipMemsetAsync(p.tbuf, 0, (size_t)B * 8 * sizeof(unsigned long long), st));
+  QD_HIP(hipMalloc(&p.tbuf, (size_t)B * QD_TSTRIDE * sizeof(unsigned long long)));
+  QD_HIP(hipMemsetAsync(p.tbuf, 0, (size_t)B * QD_TSTRIDE * sizeof(unsigned long long), st));
 #endif
   note_path("glf_eig");
   hipLaunchKernelGGL(lindblad_eig_kernel, dim3(B), dim3(CG_WG), 0, st, p);
@@ -83,7 +83,7 @@ extern "C" int qd_lindblad_rk4_eig(const qd_c128* lam, const qd_c128* V, const q
   if (pad && (rc = glf_unpad(rho_p, (c128*)rho, B, N, Np, st))) return rc;
 #ifdef QD_PHASE_TIMING
   {   // diagnostics build: per-phase clocks to stderr (waits on the host)
-    std::vector<unsigned long long> t((size_t)B * 8);
+    std::vector<unsigned long long> t((size_t)B * QD_TSTRIDE);
     QD_HIP(hipStreamSynchronize(st));
     QD_HIP(hipMemcpy(t.data(), p.tbuf, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     (void)hipFree(p.tbuf);
@@ -95,15 +95,27 @@ extern "C" int qd_lindblad_rk4_eig(const qd_c128* lam, const qd_c128* V, const q
                  "workgroups):", N, B, nsteps);
     for (int q = 0; q < 6; ++q) {
       double s = 0;
-      for (int b = 0; b < B; ++b) s += (double)t[(size_t)b * 8 + q];
+      for (int b = 0; b < B; ++b) s += (double)t[(size_t)b * QD_TSTRIDE + q];
       std::fprintf(stderr, " %s %.2f", names[q], s / B / (khz * 1e-3) / (q == 5 ? 1 : std::max(1, nsteps)));
     }
     double cyc = 0, wt = 0;
     for (int b = 0; b < B; ++b) {
-      cyc += (double)t[(size_t)b * 8 + 6];
-      wt += (double)t[(size_t)b * 8 + 7];
+      cyc += (double)t[(size_t)b * QD_TSTRIDE + QD_TCLK];
+      wt += (double)t[(size_t)b * QD_TSTRIDE + QD_TWALL];
     }
-    std::fprintf(stderr, " | shader clock %.0f MHz\n", wt > 0 ? cyc / (wt / (khz * 1e3)) / 1e6 : 0.0);
+    const double mhz = wt > 0 ? cyc / (wt / (khz * 1e3)) / 1e6 : 0.0;
+    std::fprintf(stderr, " | shader clock %.0f MHz\n", mhz);
+    // the K loops' per-wave stamps (shader cycles, no barrier in front; the basis changes' two phases included)
+    const char* knames[6] = {"y-head", "y-ksteps", "y-wait", "x-head", "x-ksteps", "x-wait"};
+    for (int w = 0; w < 2; ++w) {
+      std::fprintf(stderr, "[qd phase timing] eig K loops, wave %d, us per step:", 4 * w);
+      for (int q = 0; q < 6; ++q) {
+        double s = 0;
+        for (int b = 0; b < B; ++b) s += (double)t[(size_t)b * QD_TSTRIDE + QD_TKLOOP + 6 * w + q];
+        std::fprintf(stderr, " %s %.2f", knames[q], mhz > 0 ? s / B / mhz / std::max(1, nsteps) : 0.0);
+      }
+      std::fprintf(stderr, "\n");
+    }
   }
 #endif
   return QD_OK;

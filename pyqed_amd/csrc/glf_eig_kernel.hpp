@@ -16,7 +16,7 @@
 // with the fixed change of variables, so in exact arithmetic the back-transformed state is the persistent kernel's;
 // in floating point it differs from it in rounding, scaled by cond(V) (guarded on the host).
 // A phase is one K-tile stream: every GEMM but its first finds its first K-tile in LDS buffer 0, put there under the
-// GEMM before it, and between the Y GEMM and the second GEMM at n_c = 1 the first two K-tiles of Y go from the
+// GEMM before it, every K-tile is staged from inside the k-steps of the tile before it (CgDmaStageHook), and between the Y GEMM and the second GEMM at n_c = 1 the first two K-tiles of Y go from the
 // accumulators into the staging buffers (eig_y_handover) instead of through memory, a drain and a cold prologue.  The
 // hand-overs and the waits and barriers each one rests on are listed in the kernel's phase loop.
 // Register budget: the second GEMM holds at most 5 live tiles (120 accumulator VGPRs); 0 spilled VGPRs, 0 B scratch
@@ -41,7 +41,7 @@ struct LindbladEigParams {
   c128* obs;         // [B][nsteps+1][ne]
   int nc, ne, nsteps;
   double dt;
-  unsigned long long* tbuf;  // [B][8] per-phase ticks (QD_PHASE_TIMING diagnostics) or null
+  unsigned long long* tbuf;  // [B][QD_TSTRIDE] per-phase ticks and K-loop stamps (QD_PHASE_TIMING diagnostics) or null
 };
 
 namespace {
@@ -206,25 +206,43 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
     // barriers; its last reader in the phase before is separated from these writes by that phase's closing barrier.
     // T = 8 n is even: every GEMM's last K-tile reads buffer 1 and buffer 0 was last read one
     // barrier earlier.  Every tile-end barrier of the two engines used here is s_waitcnt vmcnt(0) + barrier.
+    // Staging: a K-tile's eight DMA pieces per thread are issued inside the k-steps of the tile before it, two behind
+    // the fragment reads of each of its first four half k-steps (CgDmaStageHook, cgemm_dma128.hpp), not at its top.
+    // "Issued under tile t" below means there.  What every placement rests on: WAR, the tile-end barrier of tile t - 1,
+    // behind which no wave reads the target buffer again; RAW, the issuing wave's s_waitcnt vmcnt(0) at the end of
+    // tile t and the barrier behind it, the only thing that orders another wave's ds_read behind an LDS-DMA load.
+    // The special cases:
+    //   a GEMM's last tile, whole lookahead (n >= 2, and Y_c -> Y_{c+1}): the follower's tile 0 -> buffer 0 under tile
+    //     T - 1, which reads buffer 1; buffer 0 was last read at tile T - 2.
+    //   the Y GEMM's last tile at n = 1, B half alone: points 0 and 1 issue nothing, W tile 0 -> L.b[0] at points 2, 3.
+    //   tile 0 of the second GEMM with `two`: no hook at all; the only DMA in flight is the one issued behind the Y
+    //     GEMM's closing barrier (below), covered by tile 0's closing wait and barrier.
+    //   tile 2 of Y (second GEMM, n = 1): first issued under tile 1, behind tile 0's closing wait and barrier, which
+    //     complete and publish the Y stores (see (2)).
+    //   the second GEMM's last tile: nothing is issued.
+    //   issue_b_at behind the Y GEMM's closing barrier (n = 1): stays where it was, every wave its four pieces, ahead
+    //     of the raw barrier; it is no part of a K loop.
     // Invariants (keep ALL of these when editing):
-    //  (1) Y_c -> Y_{c+1} (n >= 2): the lookahead of cg_dma_block_gemm_stream, (M_{c+1}, r) tile 0.
+    //  (1) Y_c -> Y_{c+1} (n >= 2): the lookahead of cg_dma_block_gemm_stream_h, (M_{c+1}, r) tile 0.
     //  (2) last Y GEMM -> second GEMM, n = 1.  Tiles 0 and 1 of the second GEMM's A operand are columns 0 .. 31 of Y
     //      and go from the accumulators into L.a[0] and L.a[1] (eig_y_handover); the B halves are DMA: W tile 0 ->
     //      L.b[0] as the Y GEMM's lookahead, W tile 1 -> L.b[1] behind its closing barrier.
     //      WAR: L.a[0] and L.b[0] were last read at Y tile 6 and L.a[1], L.b[1] at Y tile 7; the lookahead is issued
-    //      behind tile 6's barrier, the ds_writes and the second DMA behind tile 7's (the closing one).
+    //      behind tile 6's barrier (under tile 7), the ds_writes and the second DMA behind tile 7's (the closing one).
     //      RAW: L.b[0]: the closing barrier's vmcnt(0).  L.a[0], L.a[1]: each writer's s_waitcnt lgkmcnt(0), then the
     //      raw s_barrier below, ahead of tile 0's fragment reads.  That barrier must not be a __syncthreads(): with
     //      the DMA and the Y stores in flight it would drain both.  L.b[1]: in flight across it; tile 0 reads buffer
     //      0 only and its closing s_waitcnt vmcnt(0) + barrier retire the DMA ahead of tile 1's reads.
     //      Y in memory: vmcnt counts stores, so the same tile-0 wait completes every wave's Y stores and the barrier
     //      makes all of Y (columns 32 .. 127) workgroup-visible (one CU, write-through L1) ahead of the first DMA read
-    //      of it, tile 2, issued at the top of tile 1.  Nothing is issued at the top of tile 0.
+    //      of it, tile 2, issued under tile 1.  Nothing is issued under tile 0.
     //  (3) last Y GEMM -> second GEMM, n >= 2: an ordinary lookahead of (Y_0, W_0) tile 0.  Y_0 was stored ahead of
     //      Y GEMM 1, whose seven drained tile-end barriers precede the first such lookahead; Y_{n-1} is first read at
     //      tile 8 (n - 1) - 1 of the second GEMM, behind at least seven of its drained barriers.
     //  (4) nothing between a hand-over and its reader touches the staging buffers: the Y epilogue and eig_tail store
     //      from registers.
+    //  (5) no compiler-made s_waitcnt vmcnt between a K loop's DMA pieces and a fragment read (tools/dma_waits.py on
+    //      the listing): the pieces sit behind uniform branches in blocks of their own (CgDmaStageHook).
     int tid0 = threadIdx.x;
     asm volatile("" : "+v"(tid0));
     if (tid0 == 0)
@@ -237,7 +255,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
       const c128* Mc = M + (size_t)c * NN;
       const bool last = c + 1 == n;
       cg_dma_block_gemm_stream_h(Mc, r, last ? (hand ? nullptr : Y) : Mc + NN, last ? Wm : r, c == 0, Np, Np,
-                                 Np, L, A);
+                                 Np, L, A CG_KSTAMP_ARG(tk, 0));
       QD_TMARK(0);
       c128* Yc = Y + (size_t)c * NN;
       if (hand) {
@@ -258,7 +276,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
       auto tail = [&](auto wc) {
         constexpr int W = decltype(wc)::value;
-        cg_dma_herm_d_gemm_h<W>(segs, n, Np, Np, Np, L, A, hand);
+        cg_dma_herm_d_gemm_h<W>(segs, n, Np, Np, Np, L, A, hand CG_KSTAMP_ARG(tk, 3));
         QD_TMARK(2);
         eig_tail<W>(A, r, rho, rn, lamS, lane, ag, ag, hc);
       };

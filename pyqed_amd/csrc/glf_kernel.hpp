@@ -29,7 +29,7 @@ struct LindbladParams {
   int hseg;                // Hermitian path: sum_c L_c r W_c is itself Hermitian (Lindblad C r C^+ / 2; not Redfield's
                            // sum A r Lam^+), so its redundant tiles below the diagonal may be skipped (cg_dma_herm_x_gemm)
   double dt;
-  unsigned long long* tbuf;  // [B][8] per-phase wall-clock ticks (QD_PHASE_TIMING diagnostics) or null
+  unsigned long long* tbuf;  // [B][QD_TSTRIDE] per-phase wall-clock ticks (QD_PHASE_TIMING diagnostics) or null
   int stage, rin, rout;        // split path: RK4 stage; stage input / output buffer (0 = rho, 1/2 = scratch 0/1)
   int ks, ys;                  // split path: K-splits of the k / Y phases (1 = none)
   c128* kslab;                 // [B][nb^2][ks][BT^2] partial k blocks
@@ -49,6 +49,10 @@ __host__ __device__ inline int glf_slots(int Np, int nc) { return (Np <= 128 ? 1
 // Horner coefficient of RK4 stage m (0..3): s_{m+1} = rho + dt / (4 - m) L s_m  (see the file header)
 __device__ __forceinline__ double glf_horner_coef(double dt, int stage) { return rk4_horner_coef(dt, stage); }
 
+// A workgroup's row of tbuf: 6 phase slots (wall-clock ticks between barrier marks), 12 K-loop slots (shader cycles
+// between per-wave stamps, no barrier in front: lindblad_eig_kernel, 6 of wave 0 then 6 of wave 4), shader and wall clock.
+constexpr int QD_TSTRIDE = 24, QD_TKLOOP = 6, QD_TCLK = 22, QD_TWALL = 23;
+
 #ifdef QD_PHASE_TIMING
 // Diagnostics only (p.tbuf != null): barrier, then thread 0 charges the ticks since the last mark to `slot`.
 #define QD_TMARK(slot)                                   \
@@ -62,12 +66,15 @@ __device__ __forceinline__ double glf_horner_coef(double dt, int stage) { return
   }
 #define QD_TIMING_DECL                                                                \
   unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = p.tbuf ? wall_clock64() : 0; \
+  unsigned long long tk[6] = {0, 0, 0, 0, 0, 0};   /* this wave's K-loop stamps (cgemm_dma128.hpp) */ \
   const unsigned long long t0w_ = tlast, t0c_ = clock64();
-#define QD_TIMING_FLUSH                                                     \
-  if (p.tbuf && threadIdx.x == 0) {                                         \
-    for (int q = 0; q < 6; ++q) p.tbuf[(size_t)b * 8 + q] += tacc[q];      \
-    p.tbuf[(size_t)b * 8 + 6] += clock64() - t0c_;                          \
-    p.tbuf[(size_t)b * 8 + 7] += wall_clock64() - t0w_;                     \
+#define QD_TIMING_FLUSH                                                                       \
+  if (p.tbuf && (threadIdx.x & 255) == 0)                                                     \
+    for (int q = 0; q < 6; ++q) p.tbuf[(size_t)b * QD_TSTRIDE + QD_TKLOOP + (threadIdx.x >> 8) * 6 + q] += tk[q]; \
+  if (p.tbuf && threadIdx.x == 0) {                                                           \
+    for (int q = 0; q < 6; ++q) p.tbuf[(size_t)b * QD_TSTRIDE + q] += tacc[q];               \
+    p.tbuf[(size_t)b * QD_TSTRIDE + QD_TCLK] += clock64() - t0c_;                             \
+    p.tbuf[(size_t)b * QD_TSTRIDE + QD_TWALL] += wall_clock64() - t0w_;                       \
   }
 #else
 #define QD_TMARK(slot)

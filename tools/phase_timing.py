@@ -1,5 +1,8 @@
 """Per-phase clock breakdown of the persistent Lindblad kernel (QD_PHASE_TIMING diagnostics).
-Run on the GPU box:  make -C pyqed_amd/csrc timing && QDYN_LIB=pyqed_amd/libqdyn_timing.so python tools/phase_timing.py"""
+Run on the GPU box:  make -C pyqed_amd/csrc timing && QDYN_LIB=pyqed_amd/libqdyn_timing.so python tools/phase_timing.py
+The library prints the clocks to stderr, one line per call: the six phase slots (ticks between barrier marks) and, for
+the eigenbasis kernel (N = 128, Hermitian), two more lines with the K loops' per-wave stamps of waves 0 and 4, head /
+k-steps / tile-end wait of the Y GEMM and of the second GEMM (y-head ... x-wait; cgemm_dma128.hpp, CG_KSTAMP_*)."""
 import os
 import sys
 import time
