@@ -148,7 +148,8 @@ int cgemm_splitk_slabs(const c128* A, const c128* B, int Mp, int Kp, int Np, c12
                        hipStream_t st);
 
 // Unnormalised DFT along the middle axis of the [O][L][I] grid x, in place, any L (spo_gen.hip).  *l2 != 0: four-step
-// order, X[k1 + (L / *l2) k2] at slot *l2 k1 + k2; else natural order.  O L I < 2^31.
+// order, X[k1 + (L / *l2) k2] at slot *l2 k1 + k2; else natural order.  O L I < 2^31.  fft_lines.hpp declares its two
+// halves, the plan of a shape (fft_lines_plan, no device call) and its execution (fft_lines_run).
 int fft_lines(c128* x, long O, int L, long I, bool inv, hipStream_t st, int* l2);
 
 // Observables of SPO states psi [npts][ns] (spo_observe.hip, qd_spo_observe): the electronic reduced density matrix
@@ -194,7 +195,7 @@ int spo_observer_check(const char* who, const int* dims, int ndim, int ns, long 
                        const void* rdm, const void* mom);
 
 // The split-operator runs that cross files.  spo_gen.hip: every grid the specialised power-of-two kernels of spo.hip
-// do not cover (D dims, any size), its 1D form, and the matrix exponentials of qd_spo_expm.
+// do not cover (D dims, any size) and its 1D form; spo_expm.hip: the matrix exponentials of qd_spo_expm.
 int spo_generic_run(c128* psi, const c128* expVh, const c128* expV, const c128* expK, const c128* expKy,
                     const int* dims, int D, int ns, int nsteps, int nout, const SnapSink& snap, hipStream_t st);
 int spo1d_generic_run(c128* psi, const c128* expV, const c128* expVh, const c128* expK, int nx, int B, int nt,

@@ -452,7 +452,7 @@ extern "C" int qd_spo_expv(const void* v, int v_complex, long npts, int ns, doub
   QD_CHECK_ARG(ns >= 1 && ns <= 1024, "qd_spo_expv: ns=%d outside [1, 1024]", ns);
   QD_CHECK_ARG(npts >= 0, "qd_spo_expv: npts=%ld", npts);
   if (npts == 0) return QD_OK;
-  if (ns > 2)   // scaling-and-squaring Taylor exponential of the Hermitian matrix eigh reads (spo_gen.hip)
+  if (ns > 2)   // scaling-and-squaring Taylor exponential of the Hermitian matrix eigh reads (spo_expm.hip)
     return spo_expm_run(v, v_complex, 1, npts, ns, dt, (c128*)expV_, (c128*)expVh_, (hipStream_t)stream);
   const int grid = (int)std::min<long>((npts + 255) / 256, 8192);
   if (v_complex)

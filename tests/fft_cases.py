@@ -16,7 +16,7 @@ def tol(n):
     return 64.0 * U * (1.0 + np.log2(n))
 
 
-# one class per plan of the engine (pyqed_amd/csrc/spo_gen.hip plan_kind / factor_stages / fft_lines, fft.hip)
+# one class per plan of the engine (pyqed_amd/csrc/fft_plan.hpp axis_plan / fourstep_split / fft_lines_plan, fft.hip)
 TINY = [1, 2, 3, 4, 5, 7, 9, 15]
 POW2 = [2 ** k for k in range(1, 14)]   # 16..1024: the fused Stockham kernel; 2048, 4096: LDS mixed radix; 8192: four-step
 PRIMES_7_61 = [7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61]

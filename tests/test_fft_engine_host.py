@@ -1,7 +1,7 @@
 """The any-size FFT engine (pyqed_amd/csrc/spo_gen.hip fft_lines) on the host: the flat-loop emulation
-(tools/cpu_emu/emu_spo.cpp) compiled with the host C++ compiler runs the engine's planning and index arithmetic --
-plan_kind, factor_stages, the Stockham stages, Bluestein, the four-step split, the direct DFT, the column / row tiles --
-unchanged, one thread per block.  White noise through every plan class and tile shape of tests/fft_cases.py against
+(tools/cpu_emu/emu_spo.cpp) compiled with the host C++ compiler runs the engine's planning (fft_plan.hpp; enumerated
+on its own by test_fft_plan_host.py) and index arithmetic -- the Stockham stages, Bluestein, the four-step split, the
+direct DFT, the column / row tiles -- unchanged, one thread per block.  White noise through every plan class and tile shape of tests/fft_cases.py against
 numpy.fft, with the tolerance of the GPU conformance test.  What a serial run cannot show (a missing barrier, an LDS
 overrun, device sincospi) is test_fft_conformance_gpu.py's part."""
 import ctypes

@@ -55,6 +55,24 @@ def test_spo2_axis_plans_and_layouts_match_oracle(nx, ny, axes, layout):
     assert relerr(np.array(r.psilist), np.array(pl)) < TOL
 
 
+def test_spo2_unfused_point_operators_match_oracle():
+    """6 x 600 with ns = 9: both axes are mixed-radix LDS plans, but the whole row of the last axis does not fit the
+    LDS (2 x 9 x 600 x 16 B > 160 KiB; the smallest such shape: ns M > 5120), so the passes that need every state of
+    a point run unfused -- LDS transforms on column tiles around the point-operator kernel -- on in-place layouts."""
+    from oracle import spo as osp
+    from pyqed_amd import SPO2
+    from conftest import took
+    x, y, surfaces, couplings, psi0 = spo2_model_rect(6, 600, 9)
+    sol = SPO2(x, y, mass=[1.0, 1.3], nstates=9)
+    sol.set_DPES(surfaces, couplings)
+    took("")
+    r = sol.run(psi0, dt=0.05, nt=2, nout=1)
+    got = took("")[1]
+    assert "spo_axis_mixed" in got and "spo_layout_in_place" in got and "spo_axis_direct" not in got, got
+    pl, _ = osp.spo2_strang_run(sol.exp_V_half, osp.keo_linear(sol.exp_K), psi0, 2, 1)
+    assert relerr(np.array(r.psilist), np.array(pl)) < TOL
+
+
 def test_spo2_1024_matches_reference():
     g, r, x, y = _spo2("spo2_1024")
     psi = r.psilist[-1]

@@ -1,4 +1,6 @@
-// Host build of spo_gen.hip through the flat-loop emulation shim (tools/cpu_emu/hip/hip_runtime.h).
+// Host build of spo_gen.hip (with fft_plan.hpp, fft_lds.hpp and spo_gen_kernels.hpp) through the flat-loop emulation
+// shim (tools/cpu_emu/hip/hip_runtime.h), for tests/test_fft_engine_host.py, tests/test_spo_gen_host.py and
+// tools/cpu_emu/emu_bits.py.
 #include <vector>
 #include <cstdarg>
 #include "hip/hip_runtime.h"

@@ -2,9 +2,9 @@
 """Compare two gfx950 device-assembly files kernel by kernel (needs no GPU):
 
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -S glf.hip -o new.s
-    python tools/isa_diff.py old.s new.s
+    python tools/isa_diff.py old.s new.s [new2.s ...]
 
-Per kernel: `same` or `differs` after stripping comments, whitespace and the function index of the .LBB<n>_ /
+Several new files (a translation unit split in two) are compared as their union.  Per kernel: `same` or `differs` after stripping comments, whitespace and the function index of the .LBB<n>_ /
 .Lfunc_end<n> labels; for a differing kernel whether the opcode histogram and the ordered s_waitcnt / s_barrier lines
 are equal; and each file's resource figures (VGPRs, VGPR / SGPR spills, scratch B per lane, LDS B, occupancy).
 Exit status 1 if any kernel differs or exists in one file only.
@@ -46,8 +46,10 @@ def figures(res):
     return " ".join("%s %d" % (label, res[key]) for key, label in FIELDS + (("occ", "occ"),))
 
 
-def main(old_path, new_path):
-    old, new = parse(old_path), parse(new_path)
+def main(old_path, *new_paths):
+    old, new = parse(old_path), {}
+    for path in new_paths:   # a file split in several: the old one against their union
+        new.update(parse(path))
     names = sorted(set(old) | set(new))
     filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
     shown = subprocess.run([filt] + names, capture_output=True, text=True).stdout.split("\n") if filt else names
@@ -73,6 +75,6 @@ def main(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:]))
