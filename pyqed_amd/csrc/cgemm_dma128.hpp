@@ -7,7 +7,7 @@
 // under tile t's first four half k-steps (glf_eig_kernel.hpp's engines: CgDmaStageHook); the __syncthreads() that ends
 // a tile waits for them (vmcnt(0)).  A GEMM's last K-tile stages tile 0 of its follower (lookahead), whole or its B half
 // alone; an A tile may instead come from a wave's registers in the same image (cg_dma_a_slot, the hand-overs at the end
-// of this file).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
+// of this file), and so may a B tile (cg_dma_b_slot).  The 3-product MAC (3 MFMAs per complex k-step for the 4 of cg_compute_tile):
 //   P1 += ar br ; P2 += ai bi ; P3 += (ar + ai)(br + bi) ;  re = P1 - P2, im = P3 - P1 - P2
 // with P1 / P2 in the tile's re / im registers until cg_dma_finalise.
 // Hermitian X GEMM: X = A r + sum_c B_c W_c (segment 0; segments >= 1, W = C^+ / 2) for k = X + X^+.  Only k on the
@@ -85,6 +85,26 @@ constexpr bool cg_dma_a_slot_conflict_free() {   // the 16 lanes of one ds_read_
 static_assert(cg_dma_a_slot_bijective(), "A-tile image: slots");
 static_assert(cg_dma_a_slot_conflict_free(), "A-tile image: fragment read groups");
 
+// The B-tile image, written once: element (k, col) of a [16][128] K-tile sits at 16-byte slot k * 128 + col, row-major
+// as in memory.  Its users are the DMA (element e = tid + 512 q lands lane-linearly at slot e and is loaded from
+// B[e / 128][e % 128]: cg_dma_b_k, cg_dma_b_col), the fragment read of cg_dma_ksteps, and a wave that writes rows of a
+// result into the image from registers (eig_tail, glf_eig_kernel.hpp).
+constexpr int cg_dma_b_slot(int k, int col) { return k * 128 + col; }
+constexpr int cg_dma_b_k(int e) { return e >> 7; }
+constexpr int cg_dma_b_col(int e) { return e & 127; }
+constexpr bool cg_dma_b_slot_bijective() {   // 16 x 128 onto 0 .. 2047, and the DMA's source map undoes the slot map
+  bool seen[128 * CG_KT] = {};
+  for (int k = 0; k < CG_KT; ++k)
+    for (int col = 0; col < 128; ++col) {
+      const int s = cg_dma_b_slot(k, col);
+      if (s < 0 || s >= 128 * CG_KT || seen[s]) return false;
+      if (cg_dma_b_k(s) != k || cg_dma_b_col(s) != col) return false;
+      seen[s] = true;
+    }
+  return true;
+}
+static_assert(cg_dma_b_slot_bijective(), "B-tile image: slots");
+
 // Per-thread part of the staging addresses (bytes) and the wave's first element of each 512-element load round.
 struct CgDmaStage {
   const CgSeg* segs;
@@ -98,7 +118,7 @@ struct CgDmaStage {
     // (row & 15 = (tid >> 4) & 15 for every q);  B: element e -> B[e / 128][e % 128]
     const int row = tid >> 4;
     offA = (unsigned)(row * lda + cg_dma_a_kslot(row & 15, tid & 15)) * (unsigned)sizeof(c128);
-    offB = (unsigned)((tid >> 7) * ldb + (tid & 127)) * (unsigned)sizeof(c128);
+    offB = (unsigned)(cg_dma_b_k(tid) * ldb + cg_dma_b_col(tid)) * (unsigned)sizeof(c128);
     wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
   }
   // K-tile t of the segment list -> LDS buffer buf (4 + 4 loads of 16 B per thread)
@@ -150,7 +170,8 @@ struct CgNoHook {
 // Staging under the k-steps (glf_eig_kernel.hpp's two engines): the eight pieces of the K-tile (ga, gb) -> buffer buf go
 // out two at the points 0 .. 3, the A rounds at points 0 and 1 and the B rounds at 2 and 3, each pair behind a half
 // k-step's fragment reads and under its 12 MFMAs, so that no wave opens a K-tile with eight loads in front of its first
-// fragment.  ga == nullptr: the B half alone (points 2 and 3); gb == nullptr: nothing.  Both tests are uniform
+// fragment.  ga == nullptr: the B half alone (points 2 and 3); gb == nullptr: the A half alone (points 0 and 1); both:
+// nothing.  A point holds one half's pieces only, so each takes one test.  The tests are uniform
 // branches, and they also keep the loads in basic blocks of their own: hipcc's waitcnt pass puts s_waitcnt vmcnt(0)
 // in front of an LDS read that follows LDS-DMA loads in the SAME block when it cannot tell their buffers apart (a
 // run-time buffer index), which makes the read wait for the whole DMA it was meant to run under.  tools/dma_waits.py
@@ -163,16 +184,11 @@ struct CgDmaStageHook {
   const char* gb;
   int buf;
   __device__ __forceinline__ void operator()(int p) const {
+    static_assert(4 % CG_STAGE_PER == 0, "a point's pieces belong to one half");
     if (p * CG_STAGE_PER >= 8) return;
-    if (!gb) return;
-    if (ga) {
+    if (p * CG_STAGE_PER < 4 ? !ga : !gb) return;
 #pragma unroll
-      for (int i = p * CG_STAGE_PER; i < (p + 1) * CG_STAGE_PER; ++i)
-        if (i < 4) st.piece(ga, gb, i, L, buf);
-    }
-#pragma unroll
-    for (int i = p * CG_STAGE_PER; i < (p + 1) * CG_STAGE_PER; ++i)
-      if (i >= 4) st.piece(ga, gb, i, L, buf);
+    for (int i = p * CG_STAGE_PER; i < (p + 1) * CG_STAGE_PER; ++i) st.piece(ga, gb, i, L, buf);
   }
 };
 
@@ -248,7 +264,7 @@ __device__ __forceinline__ void cg_dma_ksteps(const CgLds<128>& L, int buf, CgAc
       for (int j = 0; j < 2; ++j) {
         const int nj = h + j;
         if (((LIVE >> nj) | (LIVE >> (4 + nj))) & 1u) {
-          b[j] = L.b[buf][(kk + lk) * BT + c0[nj] + lr];
+          b[j] = L.b[buf][cg_dma_b_slot(kk + lk, c0[nj] + lr)];
           sb[j] = b[j].re + b[j].im;
         }
       }
@@ -425,8 +441,21 @@ __device__ __forceinline__ void cg_dma_finalise_live(CgAcc3& acc) {
 // cg_dma_block_gemm_stream whose follower may take the A half of its tile 0 from registers: nA == nullptr makes the
 // lookahead the B half alone (tile 0 of nB -> L.b[0]) and leaves L.a[0] and, behind the closing barrier, all of
 // buffer 1 to the caller.  L.a[0] was last read at tile T - 2, one barrier before the closing one.
+// How the GEMM finds its first K-tiles:
+//   CG_START_COLD   it heads a stream and stages its own tile 0 (a prologue: DMA round trip and barrier);
+//   CG_START_TILE0  tile 0 sits in buffer 0, staged and waited for by the GEMM before it (an ordinary lookahead);
+//   CG_START_TWO    tile 0 AND the B half of tile 1 are the caller's: tile 0 complete in buffer 0 and rows 16 .. 31 of
+//                   B complete in L.b[1] behind a barrier, B in memory possibly still being stored by any wave.  Tile
+//                   0's hook stages the A half of tile 1 alone (points 0 and 1), so no B is read from memory under
+//                   it; its closing s_waitcnt vmcnt(0) + barrier retire that DMA, complete every wave's stores of B
+//                   and make B workgroup-visible ahead of its first DMA read, tile 2, issued under tile 1.  No DMA is
+//                   in flight when the loop is entered, so tile 0 stays in the loop with its run-time buffer index: the
+//                   compiler has no LDS-DMA load to order its fragment reads behind, and the stores in flight do not
+//                   concern an LDS read (a peeled tile 0 with the A half of tile 1 in flight across the caller's
+//                   barrier was built and measured slower).
+enum CgStart { CG_START_COLD, CG_START_TILE0, CG_START_TWO };
 __device__ __forceinline__ void cg_dma_block_gemm_stream_h(const c128* A, const c128* B, const c128* nA, const c128* nB,
-                                                           bool first, int K, int lda, int ldb, CgLds<128>& L,
+                                                           CgStart start, int K, int lda, int ldb, CgLds<128>& L,
                                                            CgAcc3& acc CG_KSTAMP_PARAM) {
   constexpr int MW = CgCfg<128>::MW, NW = CgCfg<128>::NW, WC = CgCfg<128>::WC, NQ = CG_KT / 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -435,16 +464,18 @@ __device__ __forceinline__ void cg_dma_block_gemm_stream_h(const c128* A, const 
   cg_dma_zero(acc);
   const int T = K / CG_KT;
   const CgDmaStage st(nullptr, T, lda, ldb);
-  if (first) {
+  if (start == CG_START_COLD) {
     st.issue_at(A, B, 0, L, 0);
     __syncthreads();
   }
   CG_KSTAMP_TOP
   for (int t = 0; t < T; ++t) {
-    // the tile staged under this one: tile t + 1, or at the last tile the follower's tile 0, whole or its B half alone
+    // the tile staged under this one: tile t + 1 (under tile 0 of CG_START_TWO its A half alone), or at the last tile
+    // the follower's tile 0, whole or its B half alone
     const bool more = t + 1 < T;
     const char* ga = more ? cg_uniform(A + (t + 1) * CG_KT) : nA ? cg_uniform(nA) : nullptr;
     const char* gb = cg_uniform(more ? B + (size_t)(t + 1) * CG_KT * ldb : nB);
+    if (start == CG_START_TWO && t == 0) gb = nullptr;   // L.b[1] is the caller's: the A half of tile 1 alone
     const CgDmaStageHook hook{st, L, ga, gb, more ? (t + 1) & 1 : 0};
     cg_sched_fence();
     cg_dma_ksteps<0u, 0, NQ>(L, t & 1, acc, r0, c0, CG_KSTAMP_HOOK(hook));
@@ -475,10 +506,12 @@ __device__ __forceinline__ void cg_dma_a_tile_write(const CgAcc3& acc, int mi, i
 // two = false: tile 0 sits in buffer 0, staged and waited for by the GEMM before it (an ordinary lookahead).  two = true: tiles 0 AND 1 are the caller's: tile 0 complete in buffer 0
 // behind a barrier, the A half of tile 1 complete in L.a[1] behind the same barrier, the B half of tile 1 in flight to
 // L.b[1] as this wave's own DMA.  Tile 0 then issues nothing (no hook) and its closing wait and barrier cover that DMA;
-// the stream from memory starts with tile 2, issued inside tile 1; the last tile's hook issues nothing.
+// the stream from memory starts with tile 2, issued inside tile 1.  The last tile reads buffer 1 (T is even) and its
+// hook stages the A half alone of tile 0 of nA -> L.a[0], last read one barrier earlier, for a follower whose B half
+// comes from the caller's registers; nA == nullptr: it issues nothing.  The closing wait and barrier cover that DMA.
 template <int W>
-__device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, int nseg, int K, int lda, int ldb,
-                                                     CgLds<128>& L, CgAcc3& acc, bool two CG_KSTAMP_PARAM) {
+__device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, const c128* nA, int nseg, int K, int lda,
+                                                     int ldb, CgLds<128>& L, CgAcc3& acc, bool two CG_KSTAMP_PARAM) {
   constexpr unsigned SK = cg_herm_mask(W, true);
   constexpr int NQ = CG_KT / 4, R0 = 16 * (W >> 1), R1 = 16 * (7 - (W >> 1));
   const int r0[2] = {R0, R1};
@@ -500,14 +533,16 @@ __device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, int nseg
     t = 1;
   }
   for (; t < T; ++t) {
-    const char *ga = nullptr, *gb = nullptr;   // the last tile stages nothing
-    if (t + 1 < T) {
+    const char *ga = nullptr, *gb = nullptr;
+    if (t + 1 == T) {   // the follower's tile 0, A half alone, or nothing
+      if (nA) ga = cg_uniform(nA);
+    } else {
       const CgSeg sg = segs[(t + 1) / tps];
       const int kt = ((t + 1) % tps) * CG_KT;
       ga = cg_uniform(sg.A + kt);
       gb = cg_uniform(sg.B + (size_t)kt * ldb);
     }
-    const CgDmaStageHook hook{st, L, ga, gb, (t + 1) & 1};
+    const CgDmaStageHook hook{st, L, ga, gb, (t + 1) & 1};   // T even: the last tile stages into buffer 0
     cg_sched_fence();
     cg_dma_ksteps<SK, 0, NQ>(L, t & 1, acc, r0, c0, CG_KSTAMP_HOOK(hook));
     CG_KSTAMP_END

@@ -17,7 +17,10 @@
 // in floating point it differs from it in rounding, scaled by cond(V) (guarded on the host).
 // A phase is one K-tile stream: every GEMM but its first finds its first K-tile in LDS buffer 0, put there under the
 // GEMM before it, every K-tile is staged from inside the k-steps of the tile before it (CgDmaStageHook), and between the Y GEMM and the second GEMM at n_c = 1 the first two K-tiles of Y go from the
-// accumulators into the staging buffers (eig_y_handover) instead of through memory, a drain and a cold prologue.  The
+// accumulators into the staging buffers (eig_y_handover) instead of through memory, a drain and a cold prologue.  A
+// phase hands the next one its first K-tiles in the same way: rows 0 .. 31 of its result go from eig_tail's registers into
+// L.b[0] and L.b[1], the next M's K-tile 0 arrives by DMA under the second GEMM's last K-tile, and the barrier between
+// the phases drains nothing.  The
 // hand-overs and the waits and barriers each one rests on are listed in the kernel's phase loop.
 // Register budget: the second GEMM holds at most 5 live tiles (120 accumulator VGPRs); 0 spilled VGPRs, 0 B scratch
 // (tools/isa_diff.py).
@@ -81,9 +84,38 @@ __device__ __forceinline__ void eig_tile_loads(const c128* m, int lane, c128 (&q
 // written by one thread, loads first, so rn may be r or base.  The loads of r are issued behind the (P1, P2, P3) ->
 // (re, im) arithmetic and those of base once r is consumed: either set of five tiles next to all three accumulator
 // sets, or both next to two, spilled.
+// Rows 0 .. 31 of rn are the B halves of K-tiles 0 and 1 of the next phase's Y GEMM.  Besides going to memory as every
+// other row they are written into L.b[0] (rows 0 .. 15) and L.b[1] (rows 16 .. 31) in the engine's B-tile image
+// (cg_dma_b_slot), the same values from the same registers, by the roles of eig_rn_lds_upper / eig_rn_lds_mirror: compile-time
+// facts of W like every other tile role here.  The last phase of a call writes them too and nobody reads them.
+constexpr bool eig_rn_lds_upper(int R, int C, int ra, int lc) { return R < 2 && (R < C || ra <= lc); }
+constexpr bool eig_rn_lds_mirror(int R, int C, int ra, int lc) { return C < 2 && (R < C || ra < lc); }
+// Every slot of the two images has exactly one writer: rows 0 .. 15 come from waves 0 and 1 (row tile 0, all eight column
+// tiles), rows 16 .. 31 from waves 2 and 3 (row tile 1, C >= 1), tile (1, 0) from wave 0 as the conjugate transpose of its
+// tile (0, 1), and the lower triangles of (0, 0) and (1, 1) from their owners as conjugates.
+constexpr bool eig_rn_lds_one_to_one() {
+  unsigned char n[2][CG_KT * EIG_NP] = {};
+  for (int w = 0; w < 8; ++w)
+    for (int mi = 0; mi < 2; ++mi)
+      for (int nj = 0; nj < 4; ++nj) {
+        const int R = mi == 0 ? (w >> 1) : 7 - (w >> 1), C = cg_herm_ctile(w, nj);
+        if (R > C) continue;
+        for (int lane = 0; lane < 64; ++lane)
+          for (int e = 0; e < 4; ++e) {
+            const int ra = (lane >> 4) + 4 * e, lc = lane & 15;
+            if (eig_rn_lds_upper(R, C, ra, lc)) ++n[R][cg_dma_b_slot(ra, 16 * C + lc)];    // rn[16 R + ra][16 C + lc]
+            if (eig_rn_lds_mirror(R, C, ra, lc)) ++n[C][cg_dma_b_slot(lc, 16 * R + ra)];   // rn[16 C + lc][16 R + ra]
+          }
+      }
+  for (int t = 0; t < 2; ++t)
+    for (int s = 0; s < CG_KT * EIG_NP; ++s)
+      if (n[t][s] != 1) return false;
+  return true;
+}
+static_assert(eig_rn_lds_one_to_one(), "rows 0 .. 31 of rn onto L.b[0], L.b[1]: one writer per slot");
 template <int W>
 __device__ __forceinline__ void eig_tail(CgAcc3& A, const c128* r, const c128* base, c128* rn, const c128* lamS,
-                                         int lane, double a, double g, double hc) {
+                                         CgLds<128>& L, int lane, double a, double g, double hc) {
   constexpr unsigned LIVE = 0xffu & ~cg_herm_mask(W, true);
   const int lr = lane >> 4, lc = lane & 15;
   const unsigned vu = (unsigned)(lr * EIG_NP + lc) * (unsigned)sizeof(c128);
@@ -129,6 +161,10 @@ __device__ __forceinline__ void eig_tail(CgAcc3& A, const c128* r, const c128* b
         char* t = reinterpret_cast<char*>(rn + 16 * R + 4 * e) + (vm + sm);
         if (R < C || ra <= lc) *reinterpret_cast<c128*>(u) = v;
         if (R < C || ra < lc) *reinterpret_cast<c128*>(t) = cconj(v);
+        if constexpr (W < 4) {   // row tiles 0 and 1 (mi == 0 of waves 0 .. 3); the buffers are named by literals
+          if (R < 2 && eig_rn_lds_upper(R, C, ra, lc)) L.b[R & 1][cg_dma_b_slot(ra, 16 * C + lc)] = v;
+          if (R < 2 && C < 2 && eig_rn_lds_mirror(R, C, ra, lc)) L.b[C & 1][cg_dma_b_slot(lc, 16 * R + ra)] = cconj(v);
+        }
       }
     }
 }
@@ -219,7 +255,10 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
     //     GEMM's closing barrier (below), covered by tile 0's closing wait and barrier.
     //   tile 2 of Y (second GEMM, n = 1): first issued under tile 1, behind tile 0's closing wait and barrier, which
     //     complete and publish the Y stores (see (2)).
-    //   the second GEMM's last tile: nothing is issued.
+    //   the second GEMM's last tile, A half alone: the next phase's M tile 0 -> L.a[0] at points 0 and 1, nothing at 2
+    //     and 3; behind the call's last phase nothing is issued (see (6)).
+    //   tile 0 of a phase's first Y GEMM behind a hand-over (CG_START_TWO), A half alone: M tile 1 -> L.a[1] at points 0
+    //     and 1; the B halves of tiles 0 and 1 are in LDS already and rn is not read from memory before tile 2 (see (6)).
     //   issue_b_at behind the Y GEMM's closing barrier (n = 1): stays where it was, every wave its four pieces, ahead
     //     of the raw barrier; it is no part of a K loop.
     // Invariants (keep ALL of these when editing):
@@ -243,6 +282,30 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
     //      from registers.
     //  (5) no compiler-made s_waitcnt vmcnt between a K loop's DMA pieces and a fragment read (tools/dma_waits.py on
     //      the listing): the pieces sit behind uniform branches in blocks of their own (CgDmaStageHook).
+    //  (6) phase -> next phase (every phase but the call's last; the call's first phase keeps its cold prologue).  K-tiles
+    //      0 and 1 of the next Y GEMM (c = 0): the B halves are rows 0 .. 31 of rn and go from eig_tail's registers into
+    //      L.b[0] and L.b[1] (and to memory as before: later K-tiles, the epilogue and the caller read them there); the A
+    //      halves are DMA: the next M's tile 0 -> L.a[0] under the second GEMM's last tile, tile 1 -> L.a[1] under the Y
+    //      GEMM's tile 0.
+    //      WAR: L.a[0] was last read at the second GEMM's tile T - 2, one barrier ahead of the hook that issues into it;
+    //      L.b[0] at T - 2 and L.b[1] at T - 1, both ahead of the second GEMM's closing barrier, behind which eig_tail
+    //      writes; L.a[1] at T - 1, and its DMA is issued behind that barrier and the one below.
+    //      RAW: L.a[0]: the second GEMM's closing s_waitcnt vmcnt(0) + barrier.  L.b[0], L.b[1]: each writer's s_waitcnt
+    //      lgkmcnt(0), then the raw s_barrier below, ahead of tile 0's fragment reads.  That barrier must not wait for
+    //      vmcnt and must not be a __syncthreads(): it would drain the rn stores in front of tile 0 instead of under it.
+    //      L.a[1]: the Y GEMM's tile-0 wait and barrier, as for any staged tile.
+    //      rn in memory: the same tile-0 wait completes every wave's rn stores and the barrier makes rn workgroup-visible
+    //      ahead of the first DMA read of it, tile 2 (rows 32 .. 47), issued under tile 1; under tile 0 only M is read.
+    //      These are (2)'s arguments moved one GEMM later.
+    //      In place: rn may be r (basis changes, stages 1 and 2) or base (basis changes, stage 3).  Every element of r and
+    //      base is loaded by its owner before the owner stores it and its mirror (eig_tail), the Y GEMMs' DMA reads of r
+    //      were retired by their tile-end waits, and the second GEMM reads Y and W alone; the raw barrier changes none
+    //      of this, and the next phase reads rn from memory behind the drain of its tile 0 only.
+    //      The segment table: its readers (the second GEMM's hooks up to tile T - 2) are done ahead of the closing
+    //      barrier of tile T - 1, and thread 0 writes it behind the raw barrier.
+    //      Observables (ne > 0, behind the first basis change and behind every step): wg_observables reads rho from
+    //      memory, so there the phase ends in a full __syncthreads() (drain and publish); it touches sred alone, the
+    //      staged tiles stay by (4), and the next phase starts as behind any other.
     int tid0 = threadIdx.x;
     asm volatile("" : "+v"(tid0));
     if (tid0 == 0)
@@ -254,7 +317,9 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
     for (int c = 0; c < n; ++c) {
       const c128* Mc = M + (size_t)c * NN;
       const bool last = c + 1 == n;
-      cg_dma_block_gemm_stream_h(Mc, r, last ? (hand ? nullptr : Y) : Mc + NN, last ? Wm : r, c == 0, Np, Np,
+      // the call's first phase stages its own tile 0; every later one finds tile 0 and L.b[1] handed on by the phase before (6)
+      const CgStart start = c > 0 ? CG_START_TILE0 : ph == 0 ? CG_START_COLD : CG_START_TWO;
+      cg_dma_block_gemm_stream_h(Mc, r, last ? (hand ? nullptr : Y) : Mc + NN, last ? Wm : r, start, Np, Np,
                                  Np, L, A CG_KSTAMP_ARG(tk, 0));
       QD_TMARK(0);
       c128* Yc = Y + (size_t)c * NN;
@@ -274,18 +339,27 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
       int tid = threadIdx.x;
       asm volatile("" : "+v"(tid));   // the per-element index math stays inside the phase
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
+      // the next phase's M (c = 0): a stage's C~, V ahead of the change back, nothing behind the last phase
+      const c128* nM = ph + 1 == nph ? nullptr : ph + 2 == nph ? p.V : p.Ct;
       auto tail = [&](auto wc) {
         constexpr int W = decltype(wc)::value;
-        cg_dma_herm_d_gemm_h<W>(segs, n, Np, Np, Np, L, A, hand CG_KSTAMP_ARG(tk, 3));
+        cg_dma_herm_d_gemm_h<W>(segs, nM, n, Np, Np, Np, L, A, hand CG_KSTAMP_ARG(tk, 3));
         QD_TMARK(2);
-        eig_tail<W>(A, r, rho, rn, lamS, lane, ag, ag, hc);
+        eig_tail<W>(A, r, rho, rn, lamS, L, lane, ag, ag, hc);
       };
 #define QD_EW(w) \
   case w: tail(std::integral_constant<int, w>{}); break;
       switch (wave) { QD_EW(0) QD_EW(1) QD_EW(2) QD_EW(3) QD_EW(4) QD_EW(5) QD_EW(6) default: QD_EW(7) }
 #undef QD_EW
     }
-    __syncthreads();   // rn complete for the next phase's GEMMs, whose LDS-DMA stays behind this phase's reads
+    const bool watch = (ph == 0 || (!xf && stage == 3)) && p.ne > 0;   // observables on rho~: t0 and the end of every step
+    if (watch) {
+      __syncthreads();   // wg_observables reads rho from memory: the stores drained and published
+    } else {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's ds_writes of rows 0 .. 31; NOT vmcnt: see (6)
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    }
     QD_TMARK(3);
 #ifdef QD_PHASE_TIMING
     if (xf)
@@ -294,7 +368,7 @@ __global__ __launch_bounds__(CG_WG) void lindblad_eig_kernel(LindbladEigParams p
         tacc[q] = tkeep[q];
       }
 #endif
-    if ((ph == 0 || (!xf && stage == 3)) && p.ne > 0) {   // observables on rho~: t0 and the end of every step
+    if (watch) {   // touches sred alone: the staged tiles stay (4)
       wg_observables(rho, p.eT, p.ne, NN, obs + (size_t)(ph / 4) * p.ne, sred);
       __syncthreads();
       QD_TMARK(4);
