@@ -582,6 +582,45 @@ int qd_tdse_driven_rk4(const qd_c128* H0, const qd_c128* Hd, int nd,
                        const qd_c128* E, int ne, qd_c128* obs, void* stream);
 
 /*
+ * Linear vibronic coupling in Fock space, matrix-free (pyqed/mol.py:959-1262 LVC with
+ * SESolver.run on its H).  State psi[a][n_1]..[n_M], row-major, electronic index slowest and
+ * the last mode fastest (the reference's kron(el, mode_1, .., mode_M) order); nel electronic
+ * states, M modes, mode j truncated to dims[j] levels, D = nel prod_j dims[j]:
+ *   (H psi)[a,n] = sum_b Hel[a][b] psi[b,n] + (sum_j omega_j n_j) psi[a,n]
+ *                + sum_j sum_b W[j][a][b] ( sqrt(n_j / 2) psi[b,n-e_j] + sqrt((n_j+1) / 2) psi[b,n+e_j] )
+ * with the terms that leave 0 <= n_j < dims[j] dropped (x = (a + a^+)/sqrt 2, no zero-point
+ * energy).  Hel [nel][nel] and W [M][nel][nel] are device pointers and may be any complex
+ * matrices (nothing is derived by conjugation); dims [M] and omega [M] are host arrays read at
+ * call time.  1 <= nel <= 8, 1 <= M <= 6, dims[j] >= 1, D < 2^31, 1 <= B <= 65535; anything
+ * else is QD_EINVAL before any device work.
+ *
+ * qd_lvc_apply: out [B][D] = H psi [B][D] (out must not be psi).
+ *
+ * qd_lvc_rk4: nsteps RK4 steps (the Horner form of qd_tdse_rk4) of psi [B][D] in place;
+ *   snap [B][nsteps/save_every][D]  psi after steps save_every, 2 save_every, ... or NULL
+ *   obs  [B][nsteps/save_every + 1][nobs]  one record at t0 and at every snapshot, or NULL
+ *   path 0: the plan's choice, 1: staged (one launch per stage, any D), 2: resident (one
+ *   workgroup per member runs the whole call in LDS; D <= 2048, the measured crossover,
+ *   QD_EINVAL otherwise).
+ *
+ * qd_lvc_observe: obs [B][nobs], one record per state of psi [B][D].
+ *
+ * A record holds nobs = nel^2 (1 + M) + M complex values:
+ *   rho[a][b]  = sum_n psi[a,n] conj(psi[b,n])            <A x 1>   = tr(A rho)
+ *   X[j][a][b] = sum_n (x_j psi)[a,n] conj(psi[b,n])      <A x x_j> = tr(A X[j]), <x_j> = tr X[j]
+ *   nbar[j]    = sum_{a,n} n_j |psi[a,n]|^2
+ * summed in an order the shape alone fixes (no atomics): repeated calls agree bit for bit, and
+ * the records of a run equal qd_lvc_observe of the stored snapshots bit for bit, on either path.
+ */
+int qd_lvc_apply(const qd_c128* psi, qd_c128* out, int B, int nel, int M, const int* dims,
+                 const double* omega, const qd_c128* Hel, const qd_c128* W, void* stream);
+int qd_lvc_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, const double* omega,
+               const qd_c128* Hel, const qd_c128* W, double dt, int nsteps, int save_every,
+               qd_c128* snap, qd_c128* obs, int path, void* stream);
+int qd_lvc_observe(const qd_c128* psi, int B, int nel, int M, const int* dims, qd_c128* obs,
+                   void* stream);
+
+/*
  * 3D multi-state split operator (pyqed/wpd.py:1349-1411 SPO3.run, linear KEO
  * _KEO_linear wpd.py:1419-1432 = fftn over axes (0,1,2)).  psi [nx][ny][nz][ns],
  * expVh [nx][ny][nz][ns][ns], expK [nx][ny][nz]; snap [nsteps/nout][...].

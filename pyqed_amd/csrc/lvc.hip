@@ -1,0 +1,142 @@
+// lvc.hip — linear vibronic coupling in Fock space, matrix-free: qd_lvc_apply, qd_lvc_rk4, qd_lvc_observe.
+//
+// Replaces LVC.buildH + SESolver.run of pyqed/mol.py:959-1262 on a dense or sparse H by the stencil of
+// lvc_kernels.hpp.  This file is the host side only: pointer checks, the plan (lvc_plan.hpp decides what is admitted,
+// the path, every grid and the scratch layout), scratch from the arena, and the launches.  dims and omega are host
+// arrays read at call time into kernel arguments, so the calls are asynchronous and a capture holds their values.
+#include "lvc_kernels.hpp"
+
+namespace qd {
+namespace {
+
+int lvc_refused(const LvcPlan& p) {
+  set_error("%s", p.msg);
+  return QD_EINVAL;
+}
+
+LvcDev lvc_dev(const LvcPlan& p, const double* omega) {
+  LvcDev m = p.dev;
+  for (int j = 0; j < m.M; ++j) m.omega[j] = omega[j];
+  return m;
+}
+
+dim3 grid_of(const LvcLaunch& l) { return dim3(l.gx, l.gy, l.gz); }
+
+// out = base + coef (-iH) v, or out = H v (base null)
+int lvc_stage(const LvcPlan& p, const LvcDev& m, const c128* Hel, const c128* W, const c128* v, const c128* base,
+              c128* out, double coef, hipStream_t st) {
+  const bool hit = dispatch_lvc_nel(m.nel, [&](auto N) {
+    hipLaunchKernelGGL((lvc_stage_kernel<decltype(N)::value>), grid_of(p.stage), dim3(p.stage.tpb), p.stage.lds, st, m,
+                       Hel, W, v, base, out, coef);
+    return true;
+  });
+  QD_CHECK_ARG(hit, "lvc: no stage kernel for nel=%d", m.nel);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
+// the record of B states psi (members bstride apart) into obs + b * obs_bstride (complex values)
+int lvc_observe(const LvcPlan& p, const LvcDev& m, const c128* psi, size_t bstride, double* part, c128* obs,
+                size_t obs_bstride, hipStream_t st) {
+  hipLaunchKernelGGL(lvc_obs_part_kernel, grid_of(p.obs_part), dim3(p.obs_part.tpb), 0, st, m, psi, bstride, part);
+  QD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(lvc_obs_final_kernel, grid_of(p.obs_final), dim3(p.obs_final.tpb), 0, st, m.nel, m.M, p.G,
+                     (const double*)part, (double*)obs, 2 * obs_bstride);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
+int lvc_run_staged(const LvcPlan& p, const LvcDev& m, const c128* Hel, const c128* W, c128* psi, int B, double dt,
+                   int nsteps, int save_every, int nsave, c128* snap, c128* obs, hipStream_t st) {
+  void* w = nullptr;
+  QD_TRY(workspace(WS_MISC, p.ws_total, &w, st));
+  c128* x0 = (c128*)((char*)w + p.ws_x0);
+  c128* x1 = (c128*)((char*)w + p.ws_x1);
+  double* part = (double*)((char*)w + p.ws_part);
+  const size_t rec_b = (size_t)(nsave + 1) * p.nobs;
+  if (obs) QD_TRY(lvc_observe(p, m, psi, m.D, part, obs, rec_b, st));
+  const double c[4] = {dt * 0.25, dt / 3.0, dt * 0.5, dt};   // rk4_horner_coef
+  for (int s = 0; s < nsteps; ++s) {
+    QD_TRY(lvc_stage(p, m, Hel, W, psi, psi, x0, c[0], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x0, psi, x1, c[1], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x1, psi, x0, c[2], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x0, psi, psi, c[3], st));
+    if (save_every > 0 && (s + 1) % save_every == 0) {
+      const int idx = (s + 1) / save_every;
+      if (snap) {
+        hipLaunchKernelGGL(lvc_snap_kernel, grid_of(p.snap), dim3(p.snap.tpb), 0, st, (const c128*)psi, B, m.D, nsave,
+                           idx, snap);
+        QD_HIP(hipGetLastError());
+      }
+      if (obs) QD_TRY(lvc_observe(p, m, psi, m.D, part, obs + (size_t)idx * p.nobs, rec_b, st));
+    }
+  }
+  return QD_OK;
+}
+
+template <int NEL>
+int lvc_launch_resident(const LvcPlan& p, const LvcDev& m, const c128* Hel, const c128* W, c128* psi, double dt,
+                        int nsteps, int save_every, int nsave, c128* snap, c128* obs, hipStream_t st) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)lvc_resident_kernel<NEL>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LVC_LDS_MAX);
+  QD_HIP(attr);
+  const LvcLds L{(unsigned)p.lds_vec1, (unsigned)p.lds_tab, (unsigned)p.lds_wave, (unsigned)p.lds_tile,
+                 (unsigned)p.lds_nbar};
+  hipLaunchKernelGGL((lvc_resident_kernel<NEL>), grid_of(p.resident), dim3(p.resident.tpb), p.resident.lds, st, m, L,
+                     Hel, W, psi, dt, nsteps, save_every, nsave, snap, (double*)obs, p.nobs);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
+}  // namespace
+}  // namespace qd
+
+using namespace qd;
+
+extern "C" int qd_lvc_apply(const qd_c128* psi, qd_c128* out, int B, int nel, int M, const int* dims,
+                            const double* omega, const qd_c128* Hel, const qd_c128* W, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  QD_CHECK_ARG(psi && out && omega && Hel && W, "qd_lvc_apply: null pointer");
+  QD_CHECK_ARG(psi != out, "qd_lvc_apply: out must not be psi");
+  const LvcPlan p = lvc_plan("qd_lvc_apply", B, nel, M, dims);
+  if (p.refused) return lvc_refused(p);
+  return lvc_stage(p, lvc_dev(p, omega), (const c128*)Hel, (const c128*)W, (const c128*)psi, nullptr, (c128*)out, 0.0,
+                   st);
+}
+
+extern "C" int qd_lvc_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, const double* omega,
+                          const qd_c128* Hel, const qd_c128* W, double dt, int nsteps, int save_every, qd_c128* snap,
+                          qd_c128* obs, int path, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(psi && omega && Hel && W, "qd_lvc_rk4: null pointer");
+  const LvcPlan p = lvc_plan("qd_lvc_rk4", B, nel, M, dims, path, nsteps, save_every, obs != nullptr);
+  if (p.refused) return lvc_refused(p);
+  const LvcDev m = lvc_dev(p, omega);
+  const int nsave = save_every > 0 ? nsteps / save_every : 0;
+  if (p.path == LVC_RESIDENT) {
+    note_path("lvc_resident");
+    int rc = QD_OK;
+    const bool hit = dispatch_lvc_nel(nel, [&](auto N) {
+      rc = lvc_launch_resident<decltype(N)::value>(p, m, (const c128*)Hel, (const c128*)W, (c128*)psi, dt, nsteps,
+                                                   save_every, nsave, (c128*)snap, (c128*)obs, st);
+      return true;
+    });
+    QD_CHECK_ARG(hit, "qd_lvc_rk4: no resident kernel for nel=%d", nel);
+    return rc;
+  }
+  note_path("lvc_staged");
+  return lvc_run_staged(p, m, (const c128*)Hel, (const c128*)W, (c128*)psi, B, dt, nsteps, save_every, nsave,
+                        (c128*)snap, (c128*)obs, st);
+}
+
+extern "C" int qd_lvc_observe(const qd_c128* psi, int B, int nel, int M, const int* dims, qd_c128* obs, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(psi && obs, "qd_lvc_observe: null pointer");
+  const LvcPlan p = lvc_plan("qd_lvc_observe", B, nel, M, dims);
+  if (p.refused) return lvc_refused(p);
+  void* w = nullptr;
+  QD_TRY(workspace(WS_MISC, p.ws_part_bytes, &w, st));
+  return lvc_observe(p, p.dev, (const c128*)psi, p.dev.D, (double*)w, (c128*)obs, p.nobs, st);
+}

@@ -1,0 +1,153 @@
+// lvc_plan.hpp — the shape decisions of the linear-vibronic-coupling entry points (lvc.hip: qd_lvc_apply, qd_lvc_rk4,
+// qd_lvc_observe) in plain C++17, no HIP, so that a host build can enumerate them (tools/cpu_emu/lvc_plan_c.cpp,
+// tests/test_lvc_plan_host.py): what a call admits and every refusal with its message, the path (resident or staged),
+// the tile, the grids, the LDS bytes and layout of the resident kernel, the scratch layout, and the layout of the
+// observable partials.  lvc.hip executes what lvc_plan returns and decides nothing itself; lvc_kernels.hpp reads the
+// same constants.
+//
+// State psi[a][n_1]..[n_M], row-major, electronic index slowest: element (a, n) at a * nvib + n, with n the flat
+// vibrational index (last mode fastest, stride[j] = prod_{k > j} dims[k]).
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdio>
+
+#include "typed_dispatch.hpp"
+
+namespace qd {
+
+constexpr int LVC_MAX_NEL = 8;              // electronic states a thread holds in registers
+constexpr int LVC_MAX_MODES = 6;
+constexpr int LVC_TILE = 256;               // vibrational points per workgroup of the staged, apply and partial kernels
+constexpr int LVC_RES_TPB = 512;            // threads of the resident kernel: two groups of LVC_TILE
+// Resident up to the measured crossover, not wherever the LDS would fit (D = 4096): a resident step costs one CU's
+// time, linear in D and growing with M, a staged step four launches, 14-28 us flat below D = 5000.  nel = 3, us per
+// step resident / staged (tools/bench_lvc.py, profiles/lvc/): M = 1: 7.3 / 14.5 at D = 2049, 14.3 / 14.8 at 4095;
+// M = 2: 11.4 / 16.8 at 2028, 15.6 / 16.1 at 3072, 23.3 / 17.5 at 3996; M = 3: 16.0 / 19.7 at 2187, 22.2 / 18.7 at
+// 3000; M = 4: 20.3 / 22.4 at 1875, 42.7 / 22.1 at 3888; M = 6: 29.1 / 27.6 at 2187.  The smallest crossover is
+// M = 6's, just under 2187.
+constexpr long LVC_RESIDENT_MAX_D = 2048;
+constexpr int LVC_OBS_MAX_GRID = 1024;      // partial rows per (member, observable row) at most
+constexpr int LVC_OBS_NV = 2 * LVC_MAX_NEL + 1;   // doubles of one partial row: nel complex sums, then the nbar part
+constexpr int LVC_GRID_YZ_MAX = 65535;      // the largest y or z extent of a grid
+constexpr size_t LVC_LDS_MAX = 80 * 1024;   // what the resident kernel may ask for, all dynamic (a CU has 160 KiB)
+constexpr int LVC_FLAT_GRID_MAX = 4096;     // blocks of the grid-strided snapshot copy
+
+enum LvcPath { LVC_AUTO = 0, LVC_STAGED = 1, LVC_RESIDENT = 2 };
+
+// The model as the kernels take it (a kernel argument by value: nothing of it lives in device memory).
+struct LvcDev {
+  int nel, M, nvib, D;
+  int dims[LVC_MAX_MODES];
+  int stride[LVC_MAX_MODES];
+  double omega[LVC_MAX_MODES];
+};
+
+struct LvcLaunch {
+  unsigned gx, gy, gz;
+  int tpb;
+  size_t lds;   // dynamic LDS bytes
+};
+
+struct LvcPlan {
+  int refused;   // then only msg is set
+  int path;      // LVC_STAGED or LVC_RESIDENT (qd_lvc_rk4 only)
+  LvcDev dev;    // omega left zero: the caller's values go in at call time
+  int nobs;      // complex values of one observable record: nel^2 (1 + M) + M
+  int rows;      // observable rows (r, a): r = 0 rho, r = j + 1 X[j]; (1 + M) nel of them
+  int G;         // partial rows per (member, observable row): workgroup g sums the tiles g, g + G, ...
+  int kp;        // vibrational points a thread of the resident kernel owns at most
+  LvcLaunch stage;      // one Horner stage, or H psi: grid (tiles, B)
+  LvcLaunch resident;   // the whole call: grid (B)
+  LvcLaunch obs_part;   // grid (G, rows, B)
+  LvcLaunch obs_final;  // grid (B)
+  LvcLaunch snap;       // grid-strided copy of B states
+  // resident LDS in bytes from the 16-byte aligned base: two stage vectors | Hel and W | wave partials | tile partials |
+  // the nbar parts of the rows
+  size_t lds_vec1, lds_tab, lds_wave, lds_tile, lds_nbar;
+  // scratch in bytes: two stage vectors of B states | partial rows [B][rows][G][LVC_OBS_NV] doubles
+  size_t ws_x0, ws_x1, ws_part, ws_part_bytes, ws_total;   // qd_lvc_observe takes ws_part_bytes alone
+  char msg[160];
+};
+
+inline long lvc_ceil(long a, long b) { return (a + b - 1) / b; }
+inline size_t lvc_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// What the three entry points admit of a model, and the launches of a call on B states.  `fn` names the entry point in
+// the messages.  path_req, nsteps, save_every and want_obs matter to qd_lvc_rk4 only (the others pass LVC_AUTO, 0, 0 and
+// false; staged launches are what they execute).
+inline LvcPlan lvc_plan(const char* fn, long B, int nel, int M, const int* dims, int path_req = LVC_AUTO,
+                        int nsteps = 0, int save_every = 0, bool want_obs = false) {
+  LvcPlan p{};
+  p.refused = 1;
+  auto refuse = [&](auto... a) {
+    std::snprintf(p.msg, sizeof p.msg, a...);
+    return p;
+  };
+  if (!(nel >= 1 && nel <= LVC_MAX_NEL)) return refuse("%s: nel=%d outside [1, %d]", fn, nel, LVC_MAX_NEL);
+  if (!(M >= 1 && M <= LVC_MAX_MODES)) return refuse("%s: M=%d outside [1, %d]", fn, M, LVC_MAX_MODES);
+  if (!dims) return refuse("%s: null dims", fn);
+  long D = nel;
+  for (int j = 0; j < M; ++j) {
+    if (!(dims[j] >= 1)) return refuse("%s: dims[%d]=%d must be at least 1", fn, j, dims[j]);
+    if (D > ((1L << 31) - 1) / dims[j]) return refuse("%s: D = nel * prod(dims) must stay below 2^31", fn);
+    D *= dims[j];
+  }
+  if (!(B >= 1 && B <= LVC_GRID_YZ_MAX)) return refuse("%s: B=%ld outside [1, %d]", fn, B, LVC_GRID_YZ_MAX);
+  if (!(path_req >= LVC_AUTO && path_req <= LVC_RESIDENT)) return refuse("%s: path=%d outside [0, 2]", fn, path_req);
+  if (!(nsteps >= 0 && save_every >= 0))
+    return refuse("%s: nsteps=%d and save_every=%d must not be negative", fn, nsteps, save_every);
+  if (want_obs && !(save_every > 0 || nsteps == 0)) return refuse("%s: observables need save_every > 0", fn);
+  const bool fits = D <= LVC_RESIDENT_MAX_D;
+  if (path_req == LVC_RESIDENT && !fits)
+    return refuse("%s: the resident path needs D <= %ld (D = %ld)", fn, LVC_RESIDENT_MAX_D, D);
+  p.refused = 0;
+  p.path = path_req == LVC_AUTO ? (fits ? LVC_RESIDENT : LVC_STAGED) : path_req;
+
+  LvcDev& d = p.dev;
+  d.nel = nel;
+  d.M = M;
+  d.D = (int)D;
+  d.nvib = (int)(D / nel);
+  for (int j = M - 1, s = 1; j >= 0; --j) {
+    d.dims[j] = dims[j];
+    d.stride[j] = s;
+    s *= dims[j];
+  }
+  for (int j = M; j < LVC_MAX_MODES; ++j) d.dims[j] = d.stride[j] = 1;
+  p.nobs = nel * nel * (1 + M) + M;
+  p.rows = (1 + M) * nel;
+  const long tiles = lvc_ceil(d.nvib, LVC_TILE);
+  p.G = (int)std::min<long>(tiles, LVC_OBS_MAX_GRID);
+  p.kp = (int)lvc_ceil(lvc_ceil(LVC_RESIDENT_MAX_D, nel), LVC_RES_TPB);
+
+  p.stage = LvcLaunch{(unsigned)tiles, (unsigned)B, 1, LVC_TILE, (size_t)(1 + M) * nel * nel * 16};
+  p.obs_part = LvcLaunch{(unsigned)p.G, (unsigned)p.rows, (unsigned)B, LVC_TILE, 0};
+  p.obs_final = LvcLaunch{(unsigned)B, 1, 1, LVC_TILE, 0};
+  p.snap = LvcLaunch{(unsigned)std::min<long>(lvc_ceil((long)B * D, LVC_TILE), LVC_FLAT_GRID_MAX), 1, 1, LVC_TILE, 0};
+
+  if (fits) {
+    p.lds_vec1 = (size_t)D * 16;
+    p.lds_tab = 2 * p.lds_vec1;
+    p.lds_wave = p.lds_tab + (size_t)(1 + M) * nel * nel * 16;
+    p.lds_tile = p.lds_wave + lvc_align16((size_t)(LVC_RES_TPB / 64) * LVC_OBS_NV * 8);
+    p.lds_nbar = p.lds_tile + lvc_align16((size_t)lvc_ceil(LVC_RESIDENT_MAX_D, LVC_TILE) * LVC_OBS_NV * 8);
+    p.resident = LvcLaunch{(unsigned)B, 1, 1, LVC_RES_TPB, p.lds_nbar + lvc_align16((size_t)M * nel * 8)};
+  }
+
+  p.ws_x0 = 0;
+  p.ws_x1 = (size_t)B * D * 16;
+  p.ws_part = 2 * p.ws_x1;
+  p.ws_part_bytes = lvc_align16((size_t)B * p.rows * p.G * LVC_OBS_NV * 8);
+  p.ws_total = p.ws_part + p.ws_part_bytes;
+  return p;
+}
+
+// f(int_c<NEL>{}) for the plan's nel: the kernels are instantiated for 1 .. LVC_MAX_NEL
+template <typename F>
+bool dispatch_lvc_nel(int nel, F&& f) {
+  return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(nel, f);
+}
+
+}  // namespace qd

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import pickle
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -464,3 +465,432 @@ class Mol:
         """mol.py:397-412: the decay rates of the states."""
         self.gamma = gamma
         return
+
+
+# --------------------------------------------------------------------------- LVC
+LVC_PATHS = {"auto": 0, "staged": 1, "resident": 2}
+
+
+def _lvc_arrays(dims, omega):
+    d = np.ascontiguousarray(np.asarray(dims, dtype=np.intc).reshape(-1))
+    w = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).reshape(-1))
+    if d.size != w.size:
+        raise ValueError(f"lvc: {d.size} dims but {w.size} frequencies")
+    return d, w
+
+
+def lvc_apply(psi, nel, dims, omega, Hel, W):
+    """out [B, D] = H psi [B, D] of the LVC model on the GPU (qd_lvc_apply).  Hel [nel, nel], W [M, nel, nel] and psi
+    torch complex128 on one device; dims and omega host sequences."""
+    import torch
+    from . import _lib
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d, w = _lvc_arrays(dims, omega)
+    out = torch.empty_like(psi)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_apply(_lib.ptr(psi), _lib.ptr(out), psi.shape[0], int(nel), d.size, d.ctypes.data,
+                                      w.ctypes.data, _lib.ptr(Hel), _lib.ptr(W), _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_apply")
+    return out
+
+
+def lvc_nobs(nel, M):
+    return nel * nel * (1 + M) + M
+
+
+def lvc_rk4(psi, nel, dims, omega, Hel, W, dt, nsteps, save_every=0, store=True, observe=True, path="auto",
+            snap=None, obs=None):
+    """Batched matrix-free RK4 of the LVC model on the GPU (qd_lvc_rk4): psi [B, D] in place.  Returns
+    (snap [B, nsave, D] | None, obs [B, nsave + 1, nobs] | None) with nsave = nsteps // save_every; store=False keeps
+    no snapshots, observe=False no records.  path: "auto", "staged" or "resident".  snap and obs may be passed in
+    (a graph capture replays into the same buffers)."""
+    import torch
+    from . import _lib
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d, w = _lvc_arrays(dims, omega)
+    B = psi.shape[0]
+    nsave = nsteps // save_every if save_every > 0 else 0
+    if snap is None and store and nsave:
+        snap = torch.empty((B, nsave, psi.shape[1]), dtype=torch.complex128, device=dev)
+    if obs is None and observe:
+        obs = torch.empty((B, nsave + 1, lvc_nobs(int(nel), d.size)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_rk4(_lib.ptr(psi), B, int(nel), d.size, d.ctypes.data, w.ctypes.data, _lib.ptr(Hel),
+                                    _lib.ptr(W), float(dt), int(nsteps), int(save_every), _lib.ptr(snap),
+                                    _lib.ptr(obs), LVC_PATHS[path], _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_rk4")
+    return snap, obs
+
+
+def lvc_observe(psi, nel, dims):
+    """The observable records [B, nobs] of the states psi [B, D] (qd_lvc_observe): rho [nel, nel], X[j] [nel, nel] for
+    every mode, nbar [M]."""
+    import torch
+    from . import _lib
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d = np.ascontiguousarray(np.asarray(dims, dtype=np.intc).reshape(-1))
+    obs = torch.empty((psi.shape[0], lvc_nobs(int(nel), d.size)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_observe(_lib.ptr(psi), psi.shape[0], int(nel), d.size, d.ctypes.data, _lib.ptr(obs),
+                                        _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_observe")
+    return obs
+
+
+def _jump(f, i, dim, isherm=True):
+    """phys.py:513-525 as a dense array: |f><i| (+ |i><f| when isherm), one diagonal entry for f == i."""
+    A = np.zeros((dim, dim))
+    A[f, i] = 1.0
+    if isherm:
+        A[i, f] = 1.0
+    return A
+
+
+def _x_sparse(N):
+    """(a + a^+)/sqrt 2 truncated to N levels (phys.quadrature), csr."""
+    from scipy.sparse import diags
+    c = np.sqrt(np.arange(1, N) / 2.0)
+    return diags([c, c], [1, -1], shape=(N, N), format="csr")
+
+
+@dataclass
+class Mode:
+    """pyqed.mol.Mode (mol.py:952-956): couplings is a list of [[a, b], strength]."""
+    omega: float
+    couplings: list
+    truncate: int = 2
+
+
+class LVCOp:
+    """An operator of the LVC product space held as factors: A (x) 1 (mode None) or A (x) x_j (mode j), A [nel, nel].
+    What LVC.buildop, LVC.coordinate and LVC.promote(A, 'el') return; LVCSolver.run reads its expectation value from the
+    on-device record (tr(A rho) or tr(A X[j])) instead of applying a D x D matrix."""
+    __array_ufunc__ = None   # ndarray @ LVCOp comes to __rmatmul__
+
+    def __init__(self, A, dims, mode=None):
+        self.A = np.array(A.toarray() if hasattr(A, "toarray") else A, dtype=complex)
+        self.nel = self.A.shape[0]
+        self.dims = tuple(int(d) for d in dims)
+        self.mode = mode
+        if self.A.shape != (self.nel, self.nel):
+            raise ValueError(f"LVCOp: electronic factor must be square, got {self.A.shape}")
+        if mode is not None and not 0 <= mode < len(self.dims):
+            raise ValueError(f"LVCOp: mode {mode} outside [0, {len(self.dims)})")
+        D = self.nel * int(np.prod(self.dims, dtype=np.int64))
+        self.shape = (D, D)
+
+    def tocsr(self):
+        from scipy.sparse import csr_matrix, identity, kron
+        out = csr_matrix(self.A)
+        for j, N in enumerate(self.dims):
+            out = kron(out, _x_sparse(N) if j == self.mode else identity(N, format="csr"), format="csr")
+        return out
+
+    def toarray(self):
+        return self.tocsr().toarray()
+
+    def dot(self, other):
+        from scipy.sparse import issparse
+        if isinstance(other, LVCOp):
+            if other.dims != self.dims or other.nel != self.nel:
+                raise ValueError("LVCOp: product of operators on different spaces")
+            if self.mode is None or other.mode is None:
+                return LVCOp(self.A @ other.A, self.dims, self.mode if other.mode is None else other.mode)
+            return self.tocsr() @ other.tocsr()
+        if issparse(other):
+            return self.tocsr() @ other
+        v = np.asarray(other)
+        if v.shape[0] != self.shape[0]:
+            raise ValueError(f"LVCOp: operand has {v.shape[0]} rows, expected {self.shape[0]}")
+        g = v.reshape((self.nel,) + self.dims + v.shape[1:])
+        if self.mode is not None:
+            ax, N = 1 + self.mode, self.dims[self.mode]
+            c = np.sqrt(np.arange(1, N) / 2.0).reshape([N - 1 if k == ax else 1 for k in range(g.ndim)])
+            lo = tuple(slice(0, N - 1) if k == ax else slice(None) for k in range(g.ndim))
+            hi = tuple(slice(1, N) if k == ax else slice(None) for k in range(g.ndim))
+            t = np.zeros(g.shape, dtype=np.result_type(g.dtype, float))
+            t[hi] += c * g[lo]
+            t[lo] += c * g[hi]
+            g = t
+        return np.tensordot(self.A, g, axes=(1, 0)).reshape(v.shape)
+
+    def __matmul__(self, other):
+        return self.dot(other)
+
+    def __rmatmul__(self, other):
+        return other @ self.tocsr()
+
+    def from_record(self, rho, X):
+        """<psi| op |psi> from the records rho [.., nel, nel] and X [.., M, nel, nel]."""
+        R = rho if self.mode is None else X[..., self.mode, :, :]
+        return np.einsum("ab,...ba->...", self.A, R)
+
+
+class LVC:
+    """Linear vibronic coupling model in Fock space: drop-in for pyqed.mol.LVC (mol.py:959-1293).  The Hamiltonian is
+    never needed as a matrix for a run: wavepacket_dynamics() returns an LVCSolver that applies it matrix-free on the
+    GPU.  Where the reference's paths are broken we serve the evident intent: per-mode truncations
+    are honoured in buildH, one mode works, and 1 <= nel <= 8 states with 1 <= M <= 6 modes are taken; anything outside
+    raises ValueError."""
+
+    def __init__(self, E, modes):
+        E = list(np.asarray(E).reshape(-1))
+        modes = list(modes)
+        if not 1 <= len(E) <= 8:
+            raise ValueError(f"LVC: {len(E)} electronic states, 1 to 8 are supported")
+        if not 1 <= len(modes) <= 6:
+            raise ValueError(f"LVC: {len(modes)} modes, 1 to 6 are supported")
+        self.e_fc = E
+        self.nel = self.nstates = len(E)
+        self.nmodes = len(modes)
+        self.modes = modes
+        self.truncate = None
+        self.fock_dims = [int(m.truncate) for m in modes]
+        for j, N in enumerate(self.fock_dims):
+            if N < 1:
+                raise ValueError(f"LVC: mode {j} is truncated to {N} levels, at least 1 is needed")
+        self.nvib = int(np.prod(self.fock_dims, dtype=object))
+        self.dim = self.nel * self.nvib
+        if self.dim >= 2 ** 31:
+            raise ValueError(f"LVC: D = nel * prod(truncations) = {self.dim} must stay below 2^31")
+        for j, m in enumerate(modes):
+            for c in m.couplings:
+                a, b = c[0]
+                if not (0 <= a < self.nel and 0 <= b < self.nel):
+                    raise ValueError(f"LVC: mode {j} couples states ({a}, {b}) outside [0, {self.nel})")
+        self.omegas = [mode.omega for mode in self.modes]
+        self.H = None
+        self._extra = np.zeros((self.nel, self.nel), dtype=complex)   # add_coupling terms
+        self._x = None
+
+    # nvib-sized identities only when asked for
+    @property
+    def idm_vib(self):
+        from scipy.sparse import identity
+        return identity(self.nvib)
+
+    @property
+    def idm_el(self):
+        from scipy.sparse import identity
+        return identity(self.nstates)
+
+    def Hel(self):
+        """diag(E) plus every add_coupling term, [nel, nel] complex."""
+        return np.diag(np.asarray(self.e_fc, dtype=complex)) + self._extra
+
+    def Wmats(self):
+        """W [M, nel, nel]: mode j couples to x_j through sum_c strength_c jump(a_c, b_c)."""
+        W = np.zeros((self.nmodes, self.nel, self.nel), dtype=complex)
+        for j, mode in enumerate(self.modes):
+            for c in mode.couplings:
+                a, b = c[0]
+                W[j] += c[1] * _jump(a, b, self.nel)
+        return W
+
+    def _mode_op(self, j, op):
+        from scipy.sparse import identity, kron
+        out = identity(1, format="csr")
+        for k, N in enumerate(self.fock_dims):
+            out = kron(out, op if k == j else identity(N, format="csr"), format="csr")
+        return out
+
+    MAX_HOST_NNZ = 2 ** 28
+
+    def buildH(self):
+        """The vibronic Hamiltonian as a scipy sparse matrix on the host (mol.py:1003-1058), every mode at its own
+        truncation.  Not needed for a run."""
+        from scipy.sparse import csr_matrix, diags, identity, kron
+        if self.dim * (self.nel + 2 * self.nmodes * self.nel) > self.MAX_HOST_NNZ:
+            raise ValueError(f"LVC.buildH: D = {self.dim} is too large to assemble H on the host; "
+                             "wavepacket_dynamics() runs without it")
+        xs = [self._mode_op(j, _x_sparse(N)) for j, N in enumerate(self.fock_dims)]
+        hv = csr_matrix((self.nvib, self.nvib))
+        for j, N in enumerate(self.fock_dims):
+            hv = hv + self._mode_op(j, diags(np.arange(N) * self.omegas[j], format="csr"))
+        Hel, W = self.Hel(), self.Wmats()
+        real = not (np.iscomplexobj(self.e_fc) or np.any(Hel.imag) or np.any(W.imag))
+        cast = (lambda a: a.real) if real else (lambda a: a)
+        H = kron(csr_matrix(cast(Hel)), identity(self.nvib), format="csr") + \
+            kron(identity(self.nel), hv, format="csr")
+        for j in range(self.nmodes):
+            H = H + kron(csr_matrix(cast(W[j])), xs[j], format="csr")
+        self.H = H.tocsr()
+        self._x = xs
+        return self.H
+
+    def APES(self, x):
+        """Adiabatic surfaces at the point x [M]: the sorted eigenvalues of diag(E) + 1/2 sum_j omega_j x_j^2
+        + sum_j W[j] x_j (mol.py:1060-1076; the omega-linear prefactor is the reference's)."""
+        x = np.asarray(x, dtype=float).reshape(-1)
+        if x.size != self.nmodes:
+            raise ValueError(f"LVC.APES: x has {x.size} coordinates for {self.nmodes} modes")
+        V = np.diag(np.asarray(self.e_fc, dtype=complex))
+        V = V + 0.5 * np.sum(np.asarray(self.omegas) * x ** 2) * np.eye(self.nel)
+        W = self.Wmats()
+        for j in range(self.nmodes):
+            V = V + W[j] * x[j]
+        E = np.linalg.eigvals(V.real if not np.any(V.imag) else V)
+        return np.sort(E)
+
+    def calc_edip(self):
+        pass
+
+    def promote(self, A, which='el'):
+        """mol.py:1081-1088: A (x) 1_vib as an LVCOp, or 1_el (x) A as a scipy sparse matrix."""
+        from scipy.sparse import identity, kron
+        if which in ['el', 'e', 'electronic']:
+            return LVCOp(A, self.fock_dims)
+        elif which in ['v', 'vib', 'vibrational']:
+            return kron(identity(self.nstates), A)
+        return A
+
+    def vertical(self, n=1):
+        """The state created by vertical excitation to electronic state n: |n> (x) |0 .. 0> (mol.py:1090-1116)."""
+        if not 0 <= n < self.nel:
+            raise ValueError(f"LVC.vertical: state {n} outside [0, {self.nel})")
+        psi = np.zeros(self.dim, dtype=complex)
+        psi[n * self.nvib] = 1.0
+        return psi
+
+    def groundstate(self):
+        return self.vertical(n=0)
+
+    def buildop(self, i, f=None, isherm=True):
+        """|f><i| (+ |i><f| when isherm) (x) 1_vib as an LVCOp (mol.py:1130-1161)."""
+        if f is None:
+            f = i
+        return LVCOp(_jump(f, i, self.nstates, isherm), self.fock_dims)
+
+    def coordinate(self, n):
+        """1_el (x) x_n as an LVCOp (mol.py:1163-1178); needs no buildH."""
+        return LVCOp(np.eye(self.nel), self.fock_dims, mode=n)
+
+    def dpes(self, q):
+        pass
+
+    def wavepacket_dynamics(self, method='RK4'):
+        if method == 'RK4':
+            sol = LVCSolver(self)
+            sol.groundstate = self.groundstate()
+            return sol
+        else:
+            raise ValueError('The number of modes {} is not \
+                             supported.'.format(self.nmodes))
+
+    def rdm_el(self, psi):
+        """rho_ab = sum_n psi[a, n] conj(psi[b, n]) (mol.py:1222-1239)."""
+        p = np.reshape(np.asarray(psi), (self.nel, self.nvib))
+        return p.dot(p.conj().T)
+
+    def add_coupling(self, coupling):
+        """[[a, b], strength]: strength * jump(a, b) (x) 1_vib is added to the Hamiltonian (mol.py:1241-1262), built or
+        not.  Returns the updated H when buildH() has run, else None."""
+        from scipy.sparse import csr_matrix, identity, kron
+        a, b = coupling[0]
+        if not (0 <= a < self.nel and 0 <= b < self.nel):
+            raise ValueError(f"LVC.add_coupling: states ({a}, {b}) outside [0, {self.nel})")
+        term = coupling[1] * _jump(a, b, self.nel)
+        self._extra = self._extra + term
+        if self.H is not None:
+            t = term if np.iscomplexobj(coupling[1]) and np.imag(coupling[1]) != 0 else np.real(term)
+            self.H = (self.H + kron(csr_matrix(t), identity(self.nvib), format="csr")).tocsr()
+        return self.H
+
+
+class LVCSolver(SESolver):
+    """What LVC.wavepacket_dynamics() returns: SESolver whose run() propagates matrix-free on the GPU (qd_lvc_rk4).
+    self.H is the model's sparse H, built on first access (the inherited correlation functions and pulsed runs use it,
+    at sizes the dense path can hold)."""
+
+    def __init__(self, model):
+        self.model = model
+        self._H = None
+        self.groundstate = None
+
+    @property
+    def H(self):
+        if self._H is None:
+            self._H = self.model.H if self.model.H is not None else self.model.buildH()
+        return self._H
+
+    @H.setter
+    def H(self, value):
+        self._H = value
+
+    def run_batch(self, psi0s, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, store_states=True, device=None,
+                  path="auto"):
+        """run() for the rows of psi0s [B, D] in one call: a list of B results."""
+        import torch
+        from ._util import default_device, issparse, to_numpy
+        m = self.model
+        e_ops = [] if e_ops is None else list(e_ops)
+        for i, op in enumerate(e_ops):
+            if isinstance(op, LVCOp):
+                if op.shape[0] != m.dim or op.nel != m.nel:
+                    raise ValueError(f"e_ops[{i}] acts on another space than the model's")
+            elif not store_states:
+                raise TypeError(f"e_ops[{i}] is no LVCOp: with store_states=False only LVCOp observables, read from "
+                                "the on-device record, can be evaluated")
+            elif tuple(op.shape) != (m.dim, m.dim):
+                raise ValueError(f"e_ops[{i}] has shape {tuple(op.shape)}, expected {(m.dim, m.dim)}")
+        p0 = to_numpy(psi0s, np.complex128)
+        if p0.ndim != 2 or p0.shape[1] != m.dim:
+            raise ValueError(f"psi0s must be [B, {m.dim}], got {p0.shape}")
+        B = p0.shape[0]
+        dev = torch.device(device) if device is not None else default_device()
+        nblk = Nt // nout
+        nsteps = max(nblk - 1, 0) * nout
+        psi = torch.from_numpy(np.ascontiguousarray(p0).copy()).to(dev)
+        Hel = torch.from_numpy(np.ascontiguousarray(m.Hel())).to(dev)
+        W = torch.from_numpy(np.ascontiguousarray(m.Wmats())).to(dev)
+        snap, obs = lvc_rk4(psi, m.nel, m.fock_dims, m.omegas, Hel, W, dt, nsteps, save_every=nout, store=store_states,
+                            path=path)
+        rec = obs.cpu().numpy()[:, :nblk]
+        nn, M = m.nel * m.nel, m.nmodes
+        rho = rec[..., :nn].reshape(B, -1, m.nel, m.nel)
+        X = rec[..., nn:nn * (1 + M)].reshape(B, -1, M, m.nel, m.nel)
+        nbar = rec[..., nn * (1 + M):].real
+        states = snap.cpu().numpy() if snap is not None else None
+        final = psi.cpu().numpy()
+        results = []
+        for b in range(B):
+            result = Result(dt=dt, Nt=Nt, psi0=p0[b].copy(), t0=t0, nout=nout)
+            observables = np.zeros((nblk, len(e_ops)), dtype=complex)
+            if store_states:
+                result.psilist = [p0[b].copy()] + ([states[b, k] for k in range(states.shape[1])]
+                                                   if states is not None else [])
+            for i, op in enumerate(e_ops):
+                if isinstance(op, LVCOp):
+                    observables[:, i] = op.from_record(rho[b], X[b])
+                else:
+                    A = op if issparse(op) else np.asarray(op)
+                    observables[:, i] = [np.vdot(s, A @ s) for s in result.psilist[:nblk]]
+            result.observables = observables
+            result.psi = final[b]
+            result.rdm_el = rho[b]
+            result.x = np.einsum("kjaa->kj", X[b])
+            result.nbar = nbar[b]
+            results.append(result)
+        return results
+
+    def run(self, psi0=None, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, store_states=True, device=None, edip=None,
+            pulse=None, use_sparse=True, path="auto"):
+        """mol.py:1392-1459 with _quantum_dynamics's counts: (Nt//nout - 1) * nout steps, psilist = [psi0] + the state
+        after every nout steps, observables (Nt//nout, n_e).  LVCOp e_ops come from the on-device record, any other
+        matrix is applied on the host to the stored states.  result.rdm_el [Nt//nout, nel, nel], result.x and
+        result.nbar [Nt//nout, M] come with every run.  store_states=False keeps and copies no state.  With a pulse the
+        run falls through to SESolver.run on self.H."""
+        if psi0 is None:
+            psi0 = self.groundstate
+        if pulse is not None:
+            e_host = None if e_ops is None else [op.tocsr() if isinstance(op, LVCOp) else op for op in e_ops]
+            return SESolver.run(self, psi0=psi0, dt=dt, Nt=Nt, e_ops=e_host, nout=nout, t0=t0, edip=edip, pulse=pulse,
+                                use_sparse=use_sparse)
+        p0 = np.asarray(psi0.toarray() if hasattr(psi0, "toarray") else psi0, dtype=complex).reshape(1, -1)
+        result = self.run_batch(p0, dt=dt, Nt=Nt, e_ops=e_ops, nout=nout, t0=t0, store_states=store_states,
+                                device=device, path=path)[0]
+        result.psi0 = psi0
+        return result

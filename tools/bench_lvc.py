@@ -1,0 +1,131 @@
+#!/usr/bin/env python
+"""Time per RK4 step of the matrix-free LVC propagation (qd_lvc_rk4) on each path the plan admits, for nel = 3 on
+16^2, 24^3, 16^4, 32^4 and 20^5 vibrational levels, the shapes next to the resident limit, and, where a dense H fits
+(D <= 8192), the existing dense tdse_rk4 on the same model.  Stand-alone; bench.py is the flagship benchmark.
+
+One JSON line per (shape, path): the median, minimum and maximum over --repeats timed windows of the time per step
+(device events around one call of `steps` steps, after a warm-up call of the same shape), and the effective rate
+4 * 3 * 16 B * D / t: four stages, each at least reading v and psi and writing out once.
+
+    python tools/bench_lvc.py [--repeats 5] [--window 0.3] [--out profiles/lvc/bench_lvc.jsonl]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(3, (16, 16)), (3, (24, 24, 24)), (3, (16, 16, 16, 16)), (3, (32, 32, 32, 32)), (3, (20, 20, 20, 20, 20)),
+          # next to the resident limit (lvc_plan.hpp LVC_RESIDENT_MAX_D) in one, two, four and six modes
+          (3, (682,)), (3, (26, 26)), (3, (5, 5, 5, 5)), (3, (3, 3, 3, 3, 3, 2)), (3, (37, 37))]
+DENSE_MAX_D = 8192
+
+
+def model(nel, dims, seed=0):
+    """A Hermitian model with couplings of the size of the frequencies (the timing does not depend on the values)."""
+    rng = np.random.default_rng(seed)
+    M = len(dims)
+    omega = rng.uniform(0.05, 0.15, M)
+    Hel = np.diag(np.linspace(0.0, 1.0, nel)).astype(complex)
+    a = rng.standard_normal((M, nel, nel)) * 0.05
+    W = ((a + a.transpose(0, 2, 1)) / 2).astype(complex)
+    return omega, Hel, W
+
+
+def h_bound(dims, omega, Hel, W):
+    b = np.abs(Hel).sum(axis=0).max() + sum(w * (N - 1) for w, N in zip(omega, dims))
+    return float(b + sum(np.abs(W[j]).sum(axis=0).max() * 2 * np.sqrt(N / 2) for j, N in enumerate(dims)))
+
+
+def dense_h(nel, dims, omega, Hel, W):
+    """The dense H [D, D] of the model, for the dense tdse_rk4 comparison."""
+    from pyqed_amd import LVCOp
+    H = LVCOp(Hel, dims).toarray()
+    for j in range(len(dims)):
+        H = H + LVCOp(W[j], dims, mode=j).toarray()
+    levels = np.indices(dims).reshape(len(dims), -1)
+    return H + np.diag(np.tile(np.asarray(omega) @ levels, nel))
+
+
+def time_call(torch, fn, steps):
+    """Seconds per step of fn(steps), by device events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn(steps)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / steps
+
+
+def measure(torch, fn, window, repeats):
+    fn(2)                                   # warm-up: code objects, scratch
+    torch.cuda.synchronize()
+    t = time_call(torch, fn, 8)
+    steps = int(min(max(window / max(t, 1e-9), 8), 50000))
+    ts = [time_call(torch, fn, steps) for _ in range(repeats)]
+    return steps, float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.3, help="seconds of work per timed call")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--shapes", default=None, help='e.g. "16,16;24,24,24" (nel = 3)')
+    args = ap.parse_args()
+    import torch
+    from pyqed_amd import _lib
+    from pyqed_amd.mol import lvc_rk4, tdse_rk4
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_lvc needs a GPU: no timing is taken on a CPU")
+    dev = torch.device("cuda", 0)
+    shapes = SHAPES if args.shapes is None else [(3, tuple(int(v) for v in s.split(","))) for s in
+                                                 args.shapes.split(";")]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    lines = []
+    for nel, dims in shapes:
+        D = nel * int(np.prod(dims))
+        omega, Hel, W = model(nel, dims)
+        dt = 0.5 / h_bound(dims, omega, Hel, W)
+        Hd, Wd = t(Hel), t(W)
+        psi0 = torch.zeros((1, D), dtype=torch.complex128, device=dev)
+        psi0[0, (nel - 1) * (D // nel)] = 1.0
+        runs = []
+        for path in ("staged", "resident"):
+            psi = psi0.clone()
+
+            def fn(steps, psi=psi, path=path):
+                lvc_rk4(psi, nel, dims, omega, Hd, Wd, dt, steps, observe=False, path=path)
+            try:
+                fn(1)
+            except ValueError:              # the plan does not admit the path at this D
+                continue
+            _lib.take_path()
+            runs.append((f"lvc_{path}", fn))
+        if D <= DENSE_MAX_D:
+            H = t(dense_h(nel, dims, omega, Hel, W))
+            psi = psi0.clone()
+            runs.append(("tdse_rk4_dense", lambda steps, psi=psi, H=H: tdse_rk4(H, psi, dt, steps)))
+        for name, fn in runs:
+            steps, med, lo, hi = measure(torch, fn, args.window, args.repeats)
+            rec = {"bench": "lvc", "nel": nel, "dims": list(dims), "D": D, "vector_MiB": D * 16 / 2 ** 20,
+                   "path": name, "steps": steps, "repeats": args.repeats, "us_per_step": med * 1e6,
+                   "us_per_step_min": lo * 1e6, "us_per_step_max": hi * 1e6,
+                   "effective_TBps": 4 * 3 * 16 * D / med / 1e12}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
