@@ -95,8 +95,9 @@ int qd_workspace_stats(size_t* reserved, size_t* used);
  *       QD_GLF_SPLIT (a workgroup per output block and phase; pair blocks for
  *       Hermitian batches), QD_GLF_PERSISTENT (a workgroup per matrix),
  *       QD_GLF_EIG (the caller of qd_lindblad_rk4_eig takes it at any batch
- *       size; the other entry points dispatch by shape under it); for
- *       comparing the paths on one input;
+ *       size; the other entry points dispatch by shape under it),
+ *       QD_GLF_EIG_JUMP (likewise for the caller of qd_lindblad_rk4_eig_jump);
+ *       for comparing the paths on one input;
  *   QD_OPT_IDLE_CAP_MIB (no environment variable, default -1 = 16384): the
  *       scratch arena's idle cache in MiB -- idle slabs beyond it are released once
  *       their last user has completed (tests lower it to exercise the release).
@@ -112,6 +113,7 @@ int qd_workspace_stats(size_t* reserved, size_t* used);
 #define QD_GLF_SPLIT 2
 #define QD_GLF_PERSISTENT 3
 #define QD_GLF_EIG 4
+#define QD_GLF_EIG_JUMP 5
 int qd_set_option(int opt, int value);
 int qd_get_option(int opt, int* value);      /* value: host pointer */
 int qd_take_path(char* buf, size_t len);     /* buf: host pointer   */
@@ -188,6 +190,36 @@ int qd_lindblad_rk4_eig(const qd_c128* lam, const qd_c128* V,
                         const qd_c128* Vinv, const qd_c128* Ct, int nc,
                         qd_c128* rho, int B, int N, double dt, int nsteps,
                         const qd_c128* Et, int ne, qd_c128* obs, void* stream);
+
+/*
+ * The same propagation for EXACTLY Hermitian rho and ONE collapse operator in
+ * the eigenbasis of that operator,
+ *     C = W diag(mu) W^-1
+ * (the caller diagonalises C once per (H, C) on the host).  With
+ * rho~ = W^-1 rho W^-+ and A~ = W^-1 A W, A = -iH - 1/2 C^+ C,
+ *     d rho~/dt = X + X^+ + M o rho~ ,  X = A~ rho~ ,  M_ij = mu_i conj(mu_j):
+ * the dissipator is an elementwise product and the A term ONE full GEMM, 64
+ * tile-GEMMs per stage for the 100 of qd_lindblad_rk4_eig at one collapse
+ * operator.  The call transforms rho to rho~, runs nsteps Horner RK4 steps and
+ * transforms back; one workgroup per matrix (kernel path "glf_eig_jump").
+ *   mu    [128]            eigenvalues of C, zero beyond N
+ *   At    [128][128]       A~, zero beyond N
+ *   W, Winv [128][128]     W and W^-1, identity block beyond N
+ *   Et    [ne][128][128]   E~_m = W^+ E_m W, zero beyond N (Tr(E rho) = Tr(E~ rho~))
+ *   rho   [B][N][N], obs [B][nsteps+1][ne] as qd_lindblad_rk4; no snapshots
+ * Constraints: 64 < N <= 128.  The operands must stay valid until the stream
+ * has passed the call.  Stream-ordered; no host wait.
+ * Numerics: as qd_lindblad_rk4_eig with cond_2(W) in place of cond_2(V); the
+ * caller bounds cond_2(W) and the residual |W diag(mu) W^-1 - C| / |C| and keeps
+ * the other paths for operators that fail (a defective C: lowering operators).
+ * Every Hermitian or normal C has cond_2(W) = 1.  The result is exactly
+ * Hermitian with an exactly real diagonal.
+ */
+int qd_lindblad_rk4_eig_jump(const qd_c128* mu, const qd_c128* At,
+                             const qd_c128* W, const qd_c128* Winv,
+                             qd_c128* rho, int B, int N, double dt, int nsteps,
+                             const qd_c128* Et, int ne, qd_c128* obs,
+                             void* stream);
 
 /*
  * Driven Lindblad RK4 (pyqed/oqs.py:1699-1806 _lindblad_driven):

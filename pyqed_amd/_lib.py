@@ -27,7 +27,7 @@ QD_OPT_COOP_LAUNCH = 0
 QD_OPT_FAKE_TIMEOUT = 1
 QD_OPT_GLF_PATH = 2
 QD_OPT_IDLE_CAP_MIB = 3
-GLF_PATHS = {"auto": 0, "single": 1, "split": 2, "persistent": 3, "eig": 4}
+GLF_PATHS = {"auto": 0, "single": 1, "split": 2, "persistent": 3, "eig": 4, "eig_jump": 5}
 
 c_int = ctypes.c_int
 c_double = ctypes.c_double
@@ -54,6 +54,8 @@ SIGNATURES = {
                                      c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "qd_lindblad_rk4_eig": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double,
                                     c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "qd_lindblad_rk4_eig_jump": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                         c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "qd_glf_rk4_herm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_int,
                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "qd_glf_rk4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double,
@@ -181,6 +183,10 @@ SIGNATURES = {
                                        c_double, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
+# Entry points a library named by QDYN_LIB may lack (an earlier build kept for alternated runs): their callers test
+# has_symbol() and fall through to the path they took before.
+OPTIONAL_SYMBOLS = frozenset({"qd_lindblad_rk4_eig_jump"})
+
 _lib = None
 _lock = threading.Lock()
 _inited_devices: set[int] = set()
@@ -198,11 +204,18 @@ def load() -> ctypes.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (make -C pyqed_amd/csrc)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+                continue   # an older library (QDYN_LIB): has_symbol() is False and the caller takes another path
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
         _lib = lib
         return lib
+
+
+def has_symbol(name: str) -> bool:
+    """Whether the loaded library exports `name` (the entry points of OPTIONAL_SYMBOLS may be absent)."""
+    return hasattr(load(), name)
 
 
 def last_error() -> str:

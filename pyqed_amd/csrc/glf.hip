@@ -586,9 +586,9 @@ int glf_run(GlfSource src, const c128* H, const c128* C, const c128* P, const c1
   //  - else the persistent kernel (a workgroup per matrix).
   constexpr bool HSPLIT_Y64 = true;   // the Hermitian pair path's Y launch on 64-blocks (below)
   constexpr long SPLIT_MINWG = 512;   // workgroups per launch that a split-path block size must still give
-  // QD_GLF_EIG is taken by the caller of qd_lindblad_rk4_eig (glf_eig.hip); a call that arrives here under it is
-  // dispatched by its shape
-  const int force = option(QD_OPT_GLF_PATH) == QD_GLF_EIG ? QD_GLF_AUTO : option(QD_OPT_GLF_PATH);
+  // QD_GLF_EIG is taken by the caller of qd_lindblad_rk4_eig (glf_eig.hip) and QD_GLF_EIG_JUMP by the caller of
+  // qd_lindblad_rk4_eig_jump (glf_eig_jump.hip); a call that arrives here under either is dispatched by its shape
+  const int force = option(QD_OPT_GLF_PATH) >= QD_GLF_EIG ? QD_GLF_AUTO : option(QD_OPT_GLF_PATH);
   int split_bt = 0;
   bool hsplit = false;
   {

@@ -351,7 +351,7 @@ extern "C" {
 
 int qd_set_option(int opt, int value) {
   QD_CHECK_ARG(opt >= 0 && opt < QD_OPT_COUNT, "qd_set_option: unknown option %d", opt);
-  QD_CHECK_ARG(opt != QD_OPT_GLF_PATH || (value >= QD_GLF_AUTO && value <= QD_GLF_EIG),
+  QD_CHECK_ARG(opt != QD_OPT_GLF_PATH || (value >= QD_GLF_AUTO && value <= QD_GLF_EIG_JUMP),
                "qd_set_option: QD_OPT_GLF_PATH value %d", value);
   QD_CHECK_ARG(opt != QD_OPT_IDLE_CAP_MIB || value >= -1, "qd_set_option: QD_OPT_IDLE_CAP_MIB value %d", value);
   (void)qd::g_opt_init;

@@ -135,39 +135,125 @@ def build_eig_plan(H, cs) -> EigPlan:
     return EigPlan(H, cs)
 
 
+# --------------------------------------------------------------------------- jump-basis plan (qd_lindblad_rk4_eig_jump)
+# With ONE collapse operator the batch is propagated in the eigenbasis of that operator instead, C = W diag(mu) W^-1:
+# with rho~ = W^-1 rho W^-+ and A~ = W^-1 A W the dissipator C rho C^+ becomes the elementwise product M o rho~,
+# M_ij = mu_i conj(mu_j), and the A term ONE full GEMM, X = A~ rho~ with d rho~/dt = X + X^+ + M o rho~: 64 tile-GEMMs
+# per stage for the 100 of the A basis (include/qdyn.h).  The guards are EigPlan's, on cond_2(W) and on
+# |W diag(mu) W^-1 - C|_F / |C|_F: the conditioning sweep of tests/test_lindblad_eig_jump_plan_cpu.py keeps every
+# accepted plan within 1e-12 of the oracle.  Every Hermitian or normal C qualifies with cond 1 (pure dephasing, number
+# operators, projective measurement); a defective C (a lowering operator is nilpotent) is refused and the call runs
+# where it ran before.
+class EigJumpPlan:
+    """Host part of the plan: mu [128], W, Winv [128,128] (identity block on the padding), At [128,128] = W^-1 A W
+    (zero on the padding), cond_2(W), the residual, and ok / reason from the guards.  nc == 1 only."""
+
+    def __init__(self, H, cs):
+        import time
+        t0 = time.perf_counter()
+        H = np.asarray(H, dtype=np.complex128)
+        cs = np.asarray(cs, dtype=np.complex128).reshape(-1, H.shape[0], H.shape[0])
+        N, Np = H.shape[0], EIG_NP
+        self.N, self.nc = N, len(cs)
+        self.ok, self.reason, self.cond, self.resid, self.seconds = False, "", np.inf, np.inf, 0.0
+        if self.nc != 1:
+            self.reason = f"nc = {self.nc}: the jump basis diagonalises one collapse operator"
+            return
+        C = cs[0]
+        A = -1j * H - 0.5 * (C.conj().T @ C)
+        try:
+            # a Hermitian C through eigh: inside a degenerate eigenspace eig returns a basis that is not orthogonal
+            # (cond 194 on a +-1 spectrum where eigh gives 1)
+            self.hermitian = bool(np.array_equal(C, C.conj().T))
+            mu, W = np.linalg.eigh(C) if self.hermitian else np.linalg.eig(C)
+            mu = mu.astype(np.complex128)
+            sv = np.linalg.svd(W, compute_uv=False)
+            self.cond = float(sv[0] / sv[-1]) if sv[-1] > 0 else np.inf
+            Winv = W.conj().T.copy() if self.hermitian else np.linalg.inv(W)
+            self.resid = float(np.linalg.norm((W * mu) @ Winv - C) / max(np.linalg.norm(C), 1e-300))
+        except np.linalg.LinAlgError as e:
+            self.reason = f"eig failed: {e}"
+            return
+        finally:
+            self.seconds = time.perf_counter() - t0
+        if not (np.isfinite(self.cond) and self.cond <= EIG_MAX_COND):
+            self.reason = f"cond_2(W) = {self.cond:.3g} > {EIG_MAX_COND:g}"
+            return
+        if not (np.isfinite(self.resid) and self.resid <= EIG_MAX_RESID):
+            self.reason = f"residual {self.resid:.3g} > {EIG_MAX_RESID:g}"
+            return
+        self._W = W
+        self.mu = np.zeros(Np, np.complex128)
+        self.mu[:N] = mu
+        self.W, self.Winv = np.eye(Np, dtype=np.complex128), np.eye(Np, dtype=np.complex128)
+        self.W[:N, :N], self.Winv[:N, :N] = W, Winv
+        self.At = np.zeros((Np, Np), np.complex128)
+        self.At[:N, :N] = Winv @ A @ W
+        self.ok = True
+        self.seconds = time.perf_counter() - t0
+
+    def e_tilde(self, E):
+        """E~_m = W^+ E_m W padded with zeros: Tr(E rho) = Tr(E~ rho~) for rho~ = W^-1 rho W^-+."""
+        E = np.asarray(E, dtype=np.complex128).reshape(-1, self.N, self.N)
+        out = np.zeros((len(E), EIG_NP, EIG_NP), np.complex128)
+        for m in range(len(E)):
+            out[m, :self.N, :self.N] = self._W.conj().T @ E[m] @ self._W
+        return out
+
+
+def build_eig_jump_plan(H, cs) -> EigJumpPlan:
+    """The jump-basis plan of (H [N,N], cs [1,N,N]) from host arrays; no GPU work."""
+    return EigJumpPlan(H, cs)
+
+
 _EIG_PLANS = {}   # (id(H), id(c_ops)) -> _EigEntry; keyed and invalidated like _HERM_CHECKED
 
 
 class _EigEntry:
+    """The plans of one (H, c_ops), each built at most once: "jump" (EigJumpPlan, one collapse operator) first, "a"
+    (EigPlan) only when a caller asks for it -- the jump plan was refused or does not apply, or glf_path "eig" names
+    the A basis -- so that an accepted call pays one eigendecomposition.  A refused plan stays cached as refused."""
+
     def __init__(self, H, c_ops):
         import weakref
         self.refs = tuple((weakref.ref(t), t._version, t.data_ptr()) for t in (H, c_ops))
-        self.plan = build_eig_plan(H.cpu().numpy(), c_ops.cpu().numpy())
-        self.eops = {}
-        if self.plan.ok:
-            p = self.plan
-            self.dev = tuple(torch.from_numpy(a).to(H.device) for a in (p.lam, p.V, p.Vinv, p.Ct))
+        self.device = H.device
+        self.host = (H.cpu().numpy(), c_ops.cpu().numpy())   # until both plans exist
+        self.plans, self.dev, self.eops = {}, {}, {}
 
     def current(self, tensors):
         return all(r[0]() is t and r[1] == t._version and r[2] == t.data_ptr() for r, t in zip(self.refs, tensors))
 
-    def e_ops(self, e_ops, build):
+    def plan(self, kind, build):
+        """The plan of `kind` ("jump" or "a"), or None when it is not built yet and may not be built now."""
+        p = self.plans.get(kind)
+        if p is None and build:
+            p = self.plans[kind] = (build_eig_jump_plan if kind == "jump" else build_eig_plan)(*self.host)
+            if p.ok:
+                arrays = (p.mu, p.At, p.W, p.Winv) if kind == "jump" else (p.lam, p.V, p.Vinv, p.Ct)
+                self.dev[kind] = tuple(torch.from_numpy(a).to(self.device) for a in arrays)
+            if len(self.plans) == 2:
+                self.host = None
+        return p
+
+    def e_ops(self, kind, e_ops, build):
         import weakref
-        hit = self.eops.get(id(e_ops))
+        hit = self.eops.get((kind, id(e_ops)))
         if hit is not None and hit[0]() is e_ops and hit[1] == e_ops._version and hit[2] == e_ops.data_ptr():
             return hit[3]
         if not build:
             return None
-        Et = torch.from_numpy(self.plan.e_tilde(e_ops.cpu().numpy())).to(e_ops.device)
+        Et = torch.from_numpy(self.plans[kind].e_tilde(e_ops.cpu().numpy())).to(e_ops.device)
         if len(self.eops) > 8:
             self.eops.clear()
-        self.eops[id(e_ops)] = (weakref.ref(e_ops), e_ops._version, e_ops.data_ptr(), Et)
+        self.eops[(kind, id(e_ops))] = (weakref.ref(e_ops), e_ops._version, e_ops.data_ptr(), Et)
         return Et
 
 
-def _eig_plan_cached(H, c_ops, e_ops):
-    """(entry, Et) of an accepted plan, or None: the plan was refused by its guards (cached as refused), or the stream
-    is capturing and the plan (or E~) is not cached yet -- capture allows no host work."""
+def _eig_plan_cached(H, c_ops, e_ops, kind="a"):
+    """(device operands, Et) of an accepted plan of `kind` ("jump": mu, At, W, Winv; "a": lam, V, Vinv, Ct), or None:
+    the plan was refused by its guards (cached as refused), or the stream is capturing and the plan (or E~) is not
+    cached yet -- capture allows no host work."""
     build = not torch.cuda.is_current_stream_capturing()
     key = (id(H), id(c_ops))
     ent = _EIG_PLANS.get(key)
@@ -177,14 +263,15 @@ def _eig_plan_cached(H, c_ops, e_ops):
         if len(_EIG_PLANS) > 64:
             _EIG_PLANS.clear()
         ent = _EIG_PLANS[key] = _EigEntry(H, c_ops)
-    if not ent.plan.ok:
+    plan = ent.plan(kind, build)
+    if plan is None or not plan.ok:
         return None
     Et = None
     if e_ops is not None:
-        Et = ent.e_ops(e_ops, build)
+        Et = ent.e_ops(kind, e_ops, build)
         if Et is None:
             return None
-    return ent, Et
+    return ent.dev[kind], Et
 
 
 def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor, dt: float, nsteps: int,
@@ -214,6 +301,15 @@ def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor,
     persistent kernel, as does a call captured into a graph before its plan exists.  Results differ from the persistent
     kernel's in rounding (1e-14 relative at the benchmark's operators); the library option glf_path "persistent"
     keeps that kernel, "eig" takes the eigenbasis path at any batch size.
+
+    With ONE collapse operator the same batches are propagated in the eigenbasis of that operator instead, C = W diag(mu)
+    W^-1 (qd_lindblad_rk4_eig_jump, kernel path "glf_eig_jump"): the dissipator becomes an elementwise product and the
+    A term one full GEMM, 64 tile-GEMMs per stage.  C is diagonalised once per (H, c_ops) in place of A (eigh for a
+    Hermitian C), under the same guards on cond_2(W) and the residual; every Hermitian or normal C qualifies, a
+    defective one (a lowering operator) is refused and the call falls to the A basis and its guards as before.  The
+    result differs from the A basis's in rounding (3e-14 relative at the benchmark's operators).  glf_path "eig_jump"
+    takes this path at any batch size and raises when the call cannot run on it (nc != 1, N outside (64, 128],
+    snapshots, non-Hermitian operands); "eig" keeps meaning the A basis.
     """
     squeeze = rho.dim() == 2
     if squeeze:
@@ -242,28 +338,45 @@ def lindblad_rk4(H: torch.Tensor, c_ops: torch.Tensor | None, rho: torch.Tensor,
     h_herm = _is_hermitian_cached(H)
     glf_path = _lib.get_option(_lib.QD_OPT_GLF_PATH)
     eig_forced = glf_path == _lib.GLF_PATHS["eig"]
+    jump_forced = glf_path == _lib.GLF_PATHS["eig_jump"]
     if hermitian is None:
         min_b = HERM_NP64_MIN_BATCH if 32 < N <= 64 else HERM_SPLIT_MIN_BATCH
         # one or two trajectories at N_p = 128 with 1 or 2 collapse operators: the Hermitian single launch
         single_h = 64 < N <= 128 and B <= 2 and 1 <= nc <= 2
-        hermitian = (N <= 128 and (B >= min_b or single_h or eig_forced) and h_herm
+        hermitian = (N <= 128 and (B >= min_b or single_h or eig_forced or jump_forced) and h_herm
                      and bool(torch.equal(rho, rho.transpose(-1, -2).conj())))
     elif hermitian and not h_herm:
         raise ValueError("hermitian=True needs a Hermitian H (the X + X^+ form drops the anti-Hermitian part of H)")
     # Eigenbasis path (qd_lindblad_rk4_eig): the Hermitian gate above, 64 < N <= 128, collapse operators, no snapshots,
     # and the batch sizes at which the library would run the persistent kernel; glf_path "eig" takes it at any batch
-    # size and raises when the call cannot run on it; "persistent" (or any other forced path) keeps the other kernels.
+    # size and raises when the call cannot run on it, as "eig_jump" does for the jump basis (one collapse operator);
+    # "persistent" (or any other forced path) keeps the other kernels.
     # A plan refused by its guards, or not yet cached while the stream is capturing, leaves the call where it was.
     eig_ok = bool(hermitian) and 64 < N <= EIG_NP and 1 <= nc <= EIG_MAX_NC and not nsave
     if eig_forced and not eig_ok:
         raise ValueError('glf_path "eig" needs Hermitian H and rho, 64 < N <= 128, 1 <= nc <= 256 and no snapshots; '
                          f"got hermitian={bool(hermitian)}, N={N}, nc={nc}, save_every={save_every}")
-    if eig_ok and nsteps >= 1 and (eig_forced or (glf_path == _lib.GLF_PATHS["auto"] and B >= EIG_MIN_BATCH
-                                                  and nsteps >= EIG_MIN_STEPS)):
-        got = _eig_plan_cached(H, c_ops, e_ops)
+    if jump_forced and not (eig_ok and nc == 1):
+        raise ValueError('glf_path "eig_jump" needs Hermitian H and rho, 64 < N <= 128, one collapse operator and no '
+                         f"snapshots; got hermitian={bool(hermitian)}, N={N}, nc={nc}, save_every={save_every}")
+    if eig_ok and nsteps >= 1 and (eig_forced or jump_forced
+                                   or (glf_path == _lib.GLF_PATHS["auto"] and B >= EIG_MIN_BATCH
+                                       and nsteps >= EIG_MIN_STEPS)):
+        # the jump basis first (one collapse operator, not under "eig", a library that has the entry point); a plan
+        # refused by its guards, or not cached yet while capturing, falls to the A basis, exactly as that one falls on
+        if nc == 1 and not eig_forced and _lib.has_symbol("qd_lindblad_rk4_eig_jump"):
+            got = _eig_plan_cached(H, c_ops, e_ops, "jump")
+            if got is not None:
+                (mu, At, W, Winv), Et = got
+                with torch.cuda.device(dev):
+                    rc = _lib.load().qd_lindblad_rk4_eig_jump(_lib.ptr(mu), _lib.ptr(At), _lib.ptr(W), _lib.ptr(Winv),
+                                                              _lib.ptr(rho), B, N, float(dt), int(nsteps),
+                                                              _lib.ptr(Et), ne, _lib.ptr(obs), st)
+                _lib.check(rc, "qd_lindblad_rk4_eig_jump")
+                return obs, None
+        got = _eig_plan_cached(H, c_ops, e_ops, "a")
         if got is not None:
-            ent, Et = got
-            lam, V, Vinv, Ct = ent.dev
+            (lam, V, Vinv, Ct), Et = got
             with torch.cuda.device(dev):
                 rc = _lib.load().qd_lindblad_rk4_eig(_lib.ptr(lam), _lib.ptr(V), _lib.ptr(Vinv), _lib.ptr(Ct), nc,
                                                      _lib.ptr(rho), B, N, float(dt), int(nsteps), _lib.ptr(Et), ne,
