@@ -653,6 +653,37 @@ int qd_lvc_observe(const qd_c128* psi, int B, int nel, int M, const int* dims, q
                    void* stream);
 
 /*
+ * Laser-driven LVC run, matrix-free (pyqed/mol.py:1862-1958 driven_dynamics on the LVC H):
+ *   H(t) = H0 - sum_d f_d(t) mu_d,  mu_d = A_d (x) 1 (drive_mode[d] = -1, Condon) or
+ *                                   mu_d = A_d (x) x_j (drive_mode[d] = j in [0, M), Herzberg-Teller)
+ * is the LVC Hamiltonian with the tables Hel - sum f_d A_d and W[j] - sum f_d A_d, which the
+ * kernels rebuild from the field as the run goes.  A [nd][nel][nel] and fvals [nf][nd] are device
+ * pointers holding any complex values (nothing is derived by conjugation); drive_mode [nd] is a
+ * host array read at call time, as dims and omega are.  Drives on one table are subtracted in the
+ * order d = 0, 1, ... without contraction: identical calls agree bit for bit.  fvals is read when
+ * the kernels run, so the call is asynchronous and a captured graph replays with whatever the
+ * buffer holds at that moment.
+ *   sample 0 (hold): step s uses row s / hold of fvals, constant within the step (the reference's
+ *     rule: one field value per block of steps); the step is the Horner form of qd_lvc_rk4.
+ *     Needs nf >= ceil(nsteps / hold), hold >= 1.
+ *   sample 1 (stage): classical RK4 with the field at the stage times: row h is f(t0 + h dt / 2),
+ *     the stages of step s use rows 2s, 2s + 1, 2s + 1, 2s + 2.  Needs nf >= 2 nsteps + 1; hold
+ *     is ignored.  psi' = psi + dt/6 (k1 + 2 k2 + 2 k3 + k4).
+ * snap, obs, save_every and path as for qd_lvc_rk4 (save_every and hold are independent; the
+ * resident limit is the driven kernels' measured crossover, D <= 2048 in one to five modes and
+ * D <= 1536 in six).  nd = 0 is allowed (A, drive_mode and fvals may be NULL; fvals also when
+ * nsteps = 0 reads no row) and in hold mode equals qd_lvc_rk4.  QD_EINVAL before any device work, psi unchanged, for: nd outside
+ * [0, 8], a drive_mode entry outside [-1, M), sample outside {0, 1}, hold < 1 with sample 0, nf too
+ * small (the message says how many rows are needed), a null pointer that is needed, and
+ * everything qd_lvc_rk4 refuses.  Paths noted: lvc_driven_staged, lvc_driven_resident.
+ */
+int qd_lvc_driven_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, const double* omega,
+                      const qd_c128* Hel, const qd_c128* W, int nd, const qd_c128* A,
+                      const int* drive_mode, const qd_c128* fvals, int nf, int sample, int hold,
+                      double dt, int nsteps, int save_every, qd_c128* snap, qd_c128* obs, int path,
+                      void* stream);
+
+/*
  * 3D multi-state split operator (pyqed/wpd.py:1349-1411 SPO3.run, linear KEO
  * _KEO_linear wpd.py:1419-1432 = fftn over axes (0,1,2)).  psi [nx][ny][nz][ns],
  * expVh [nx][ny][nz][ns][ns], expK [nx][ny][nz]; snap [nsteps/nout][...].

@@ -1,4 +1,5 @@
-// lvc.hip — linear vibronic coupling in Fock space, matrix-free: qd_lvc_apply, qd_lvc_rk4, qd_lvc_observe.
+// lvc.hip — linear vibronic coupling in Fock space, matrix-free: qd_lvc_apply, qd_lvc_rk4, qd_lvc_observe and the
+// laser-driven qd_lvc_driven_rk4.
 //
 // Replaces LVC.buildH + SESolver.run of pyqed/mol.py:959-1262 on a dense or sparse H by the stencil of
 // lvc_kernels.hpp.  This file is the host side only: pointer checks, the plan (lvc_plan.hpp decides what is admitted,
@@ -88,6 +89,87 @@ int lvc_launch_resident(const LvcPlan& p, const LvcDev& m, const c128* Hel, cons
   return QD_OK;
 }
 
+// ---------------------------------------------------------------- laser-driven runs
+// the tables a driven launch takes besides the model
+struct LvcDriveArgs {
+  const c128 *Hel, *W, *A, *fvals;
+};
+
+const c128* lvc_row(const LvcDrivePlan& p, const LvcDriveArgs& t, int s, int stage) {
+  return p.drive.nd ? t.fvals + (size_t)lvc_drive_row(p.sample, p.hold, s, stage) * p.drive.nd : nullptr;
+}
+
+int lvc_run_driven_staged(const LvcDrivePlan& dp, const LvcDev& m, const LvcDriveArgs& t, c128* psi, int B, double dt,
+                          int nsteps, int save_every, int nsave, c128* snap, c128* obs, hipStream_t st) {
+  const LvcPlan& p = dp.base;
+  void* w = nullptr;
+  QD_TRY(workspace(WS_MISC, dp.ws_total, &w, st));
+  c128* x0 = (c128*)((char*)w + p.ws_x0);
+  c128* x1 = (c128*)((char*)w + p.ws_x1);
+  c128* x2 = (c128*)((char*)w + dp.ws_acc);   // stage mode only
+  double* part = (double*)((char*)w + p.ws_part);
+  const size_t rec_b = (size_t)(nsave + 1) * p.nobs;
+  if (obs) QD_TRY(lvc_observe(p, m, psi, m.D, part, obs, rec_b, st));
+  // out = base + c_out (-iH_f v) with the row of (s, stage); acc = acc_in + c_acc (-iH_f v) in stage mode
+  auto stage = [&](int s, int stg, const c128* v, c128* out, double c_out, const c128* acc_in, c128* acc,
+                   double c_acc) -> int {
+    const c128* f = lvc_row(dp, t, s, stg);
+    const bool hit = dispatch_lvc_nel(m.nel, [&](auto N) {
+      constexpr int NEL = decltype(N)::value;
+      if (dp.sample == LVC_STAGE)
+        hipLaunchKernelGGL((lvc_stage_rk4_kernel<NEL>), grid_of(p.stage), dim3(p.stage.tpb), p.stage.lds, st, m,
+                           dp.drive, t.Hel, t.W, t.A, f, v, (const c128*)psi, acc_in, out, acc, c_out, c_acc);
+      else
+        hipLaunchKernelGGL((lvc_stage_driven_kernel<NEL>), grid_of(p.stage), dim3(p.stage.tpb), p.stage.lds, st, m,
+                           dp.drive, t.Hel, t.W, t.A, f, v, (const c128*)psi, out, c_out);
+      return true;
+    });
+    QD_CHECK_ARG(hit, "qd_lvc_driven_rk4: no stage kernel for nel=%d", m.nel);
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+  };
+  const double c[4] = {dt * 0.25, dt / 3.0, dt * 0.5, dt};   // rk4_horner_coef
+  for (int s = 0; s < nsteps; ++s) {
+    if (dp.sample == LVC_STAGE) {
+      QD_TRY(stage(s, 0, psi, x0, dt * 0.5, psi, x2, dt / 6.0));
+      QD_TRY(stage(s, 1, x0, x1, dt * 0.5, x2, x2, dt / 3.0));
+      QD_TRY(stage(s, 2, x1, x0, dt, x2, x2, dt / 3.0));
+      QD_TRY(stage(s, 3, x0, nullptr, 0.0, x2, psi, dt / 6.0));
+    } else {
+      QD_TRY(stage(s, 0, psi, x0, c[0], nullptr, nullptr, 0.0));
+      QD_TRY(stage(s, 1, x0, x1, c[1], nullptr, nullptr, 0.0));
+      QD_TRY(stage(s, 2, x1, x0, c[2], nullptr, nullptr, 0.0));
+      QD_TRY(stage(s, 3, x0, psi, c[3], nullptr, nullptr, 0.0));
+    }
+    if (save_every > 0 && (s + 1) % save_every == 0) {
+      const int idx = (s + 1) / save_every;
+      if (snap) {
+        hipLaunchKernelGGL(lvc_snap_kernel, grid_of(p.snap), dim3(p.snap.tpb), 0, st, (const c128*)psi, B, m.D, nsave,
+                           idx, snap);
+        QD_HIP(hipGetLastError());
+      }
+      if (obs) QD_TRY(lvc_observe(p, m, psi, m.D, part, obs + (size_t)idx * p.nobs, rec_b, st));
+    }
+  }
+  return QD_OK;
+}
+
+template <int NEL, int SAMPLE>
+int lvc_launch_resident_driven(const LvcDrivePlan& dp, const LvcDev& m, const LvcDriveArgs& t, c128* psi, double dt,
+                               int nsteps, int save_every, int nsave, c128* snap, c128* obs, hipStream_t st) {
+  static const hipError_t attr =
+      hipFuncSetAttribute((const void*)lvc_resident_driven_kernel<NEL, SAMPLE>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LVC_DRIVE_LDS_MAX);
+  QD_HIP(attr);
+  const LvcDriveLds L{(unsigned)dp.lds_vec1, (unsigned)dp.lds_tab,  (unsigned)dp.lds_eff, (unsigned)dp.lds_drv,
+                      (unsigned)dp.lds_wave, (unsigned)dp.lds_tile, (unsigned)dp.lds_nbar};
+  hipLaunchKernelGGL((lvc_resident_driven_kernel<NEL, SAMPLE>), grid_of(dp.resident), dim3(dp.resident.tpb),
+                     dp.resident.lds, st, m, dp.drive, L, t.Hel, t.W, t.A, t.fvals, dp.hold, psi, dt, nsteps,
+                     save_every, nsave, snap, (double*)obs, dp.base.nobs);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
 }  // namespace
 }  // namespace qd
 
@@ -139,4 +221,41 @@ extern "C" int qd_lvc_observe(const qd_c128* psi, int B, int nel, int M, const i
   void* w = nullptr;
   QD_TRY(workspace(WS_MISC, p.ws_part_bytes, &w, st));
   return lvc_observe(p, p.dev, (const c128*)psi, p.dev.D, (double*)w, (c128*)obs, p.nobs, st);
+}
+
+extern "C" int qd_lvc_driven_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, const double* omega,
+                                 const qd_c128* Hel, const qd_c128* W, int nd, const qd_c128* A, const int* drive_mode,
+                                 const qd_c128* fvals, int nf, int sample, int hold, double dt, int nsteps,
+                                 int save_every, qd_c128* snap, qd_c128* obs, int path, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(psi && omega && Hel && W, "qd_lvc_driven_rk4: null pointer");
+  const LvcDrivePlan dp = lvc_drive_plan("qd_lvc_driven_rk4", B, nel, M, dims, nd, drive_mode, sample, hold, nf, path,
+                                         nsteps, save_every, obs != nullptr);
+  if (dp.refused) {
+    set_error("%s", dp.msg);
+    return QD_EINVAL;
+  }
+  // a call that reads no row (no steps) needs no fvals: an empty [0][nd] array may be null
+  QD_CHECK_ARG(nd == 0 || (A && (fvals || dp.rows_needed == 0)), "qd_lvc_driven_rk4: null A or fvals with nd=%d", nd);
+  const LvcDev m = lvc_dev(dp.base, omega);
+  const LvcDriveArgs t{(const c128*)Hel, (const c128*)W, (const c128*)A, (const c128*)fvals};
+  const int nsave = save_every > 0 ? nsteps / save_every : 0;
+  if (dp.base.path == LVC_RESIDENT) {
+    note_path("lvc_driven_resident");
+    int rc = QD_OK;
+    const bool hit = dispatch_lvc_nel(nel, [&](auto N) {
+      constexpr int NEL = decltype(N)::value;
+      rc = sample == LVC_STAGE
+               ? lvc_launch_resident_driven<NEL, 1>(dp, m, t, (c128*)psi, dt, nsteps, save_every, nsave, (c128*)snap,
+                                                    (c128*)obs, st)
+               : lvc_launch_resident_driven<NEL, 0>(dp, m, t, (c128*)psi, dt, nsteps, save_every, nsave, (c128*)snap,
+                                                    (c128*)obs, st);
+      return true;
+    });
+    QD_CHECK_ARG(hit, "qd_lvc_driven_rk4: no resident kernel for nel=%d", nel);
+    return rc;
+  }
+  note_path("lvc_driven_staged");
+  return lvc_run_driven_staged(dp, m, t, (c128*)psi, B, dt, nsteps, save_every, nsave, (c128*)snap, (c128*)obs, st);
 }

@@ -24,6 +24,10 @@
 // The resident kernel plays the partial workgroups with its two groups of LVC_TILE threads and runs the same
 // functions on its LDS copy of the state, with floating-point contraction off in both, so its in-run records equal
 // qd_lvc_observe of the stored snapshot bit for bit.  No atomics anywhere.
+//
+// Laser-driven runs (qd_lvc_driven_rk4, at the end of this file): the same stencil with tables rebuilt from a field row
+// in device memory (lvc_load_tables_driven); lvc_stage_driven_kernel and lvc_stage_rk4_kernel on the staged path,
+// lvc_resident_driven_kernel on the resident one.
 #pragma once
 
 #include "lvc_plan.hpp"
@@ -306,6 +310,205 @@ __global__ __launch_bounds__(LVC_RES_TPB) void lvc_resident_kernel(LvcDev m, Lvc
             const c128 o = cadd(base[k][a], cscale(cmulmi(y[a]), coef));
             dst[a * nvib + n] = o;
             if (stage == 3) base[k][a] = o;
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (save_every > 0 && (s + 1) % save_every == 0) {
+      const int idx = (s + 1) / save_every;
+      if (snap) {
+        c128* out = snap + ((size_t)blockIdx.x * nsave + idx - 1) * m.D;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          const int n = threadIdx.x + k * LVC_RES_TPB;
+          if (n < m.nvib) {
+#pragma unroll
+            for (int a = 0; a < NEL; ++a) out[a * nvib + n] = base[k][a];
+          }
+        }
+      }
+      if (orec) lvc_obs_resident(m, A, sh_wave, sh_tile, sh_nb, orec + (size_t)idx * nobs * 2);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const int n = threadIdx.x + k * LVC_RES_TPB;
+    if (n < m.nvib) {
+#pragma unroll
+      for (int a = 0; a < NEL; ++a) psi[a * nvib + n] = base[k][a];
+    }
+  }
+}
+
+// ---------------------------------------------------------------- laser-driven runs (qd_lvc_driven_rk4)
+// H(t) = H0 - sum_d f_d(t) mu_d, mu_d = A_d (x) 1 or A_d (x) x_j, is the same stencil with the tables
+//   Hel(t) = Hel - sum_{d: mode -1} f_d A_d,   W[j](t) = W[j] - sum_{d: mode j} f_d A_d,
+// so every kernel below is its undriven counterpart with lvc_load_tables_driven in place of lvc_load_tables and the
+// same lvc_point.  f is one row of fvals in device memory, read when the kernel runs.
+
+// byte offsets of the driven resident kernel's LDS regions (LvcDrivePlan::lds_*)
+struct LvcDriveLds {
+  unsigned vec1, tab, eff, drv, wave, tile, nbar;
+};
+
+// The effective tables of one field row into LDS (the caller synchronises): entry e of table r = e / nel^2 is
+// base[e] - sum_{d: mode[d] == r - 1} f[d] A[d][e % nel^2], the drives subtracted in the order d = 0, 1, ... without
+// contraction.  base is Hel then W ([(1 + M) nel^2], global or LDS), A [nd][nel^2] (global or LDS).  A thread builds
+// the entries e = t, t + blockDim.x, ...; dr.mode and f[d] are wave-uniform reads (kernel argument, scalar load).
+__device__ __forceinline__ void lvc_load_tables_driven(c128* tab, const c128* base_hel, const c128* base_w,
+                                                       const c128* A, const LvcDrive& dr, const c128* __restrict__ f,
+                                                       int nel, int M) {
+#pragma clang fp contract(off)
+  const int nn = nel * nel;
+  for (int e = threadIdx.x; e < (1 + M) * nn; e += blockDim.x) {
+    const int r = e / nn, q = e - r * nn;
+    c128 s = r == 0 ? base_hel[q] : base_w[e - nn];
+    for (int d = 0; d < dr.nd; ++d) {
+      if (dr.mode[d] != r - 1) continue;
+      const c128 fd = f[d], a = A[d * nn + q];
+      const double pr = fd.re * a.re - fd.im * a.im, pi = fd.re * a.im + fd.im * a.re;
+      s.re = s.re - pr;
+      s.im = s.im - pi;
+    }
+    tab[e] = s;
+  }
+}
+
+// lvc_stage_kernel with the tables of the field row f: one Horner stage out = base + coef (-iH_f) v of B states.
+// grid (ceil(nvib / LVC_TILE), B), LVC_TILE threads, dynamic LDS (1 + M) NEL^2 c128.  Aliasing as lvc_stage_kernel.
+template <int NEL>
+__global__ __launch_bounds__(LVC_TILE) void lvc_stage_driven_kernel(LvcDev m, LvcDrive dr, const c128* __restrict__ Hel,
+                                                                    const c128* __restrict__ W,
+                                                                    const c128* __restrict__ A,
+                                                                    const c128* __restrict__ f, const c128* v_g,
+                                                                    const c128* base_g, c128* out_g, double coef) {
+  extern __shared__ __attribute__((aligned(16))) char lvc_smem[];
+  c128* tab = (c128*)lvc_smem;
+  lvc_load_tables_driven(tab, Hel, W, A, dr, f, NEL, m.M);
+  __syncthreads();
+  const int n = blockIdx.x * LVC_TILE + threadIdx.x;
+  if (n >= m.nvib) return;
+  const size_t off = (size_t)blockIdx.y * m.D;
+  const c128* vin = v_g + off;
+  const size_t nvib = m.nvib;
+  c128 v[NEL], y[NEL];
+  lvc_point<NEL>(m, tab, n, [&](int b, int idx) { return vin[b * nvib + idx]; }, v, y);
+#pragma unroll
+  for (int a = 0; a < NEL; ++a) {
+    const size_t e = off + a * nvib + n;
+    out_g[e] = cadd(base_g[e], cscale(cmulmi(y[a]), coef));
+  }
+}
+
+// One classical RK4 stage with the tables of the field row f: k = -iH_f v, out = base + c_out k (skipped when out is
+// null: the last stage), acc = acc_in + c_acc k.  acc_in is base in stage 0; acc may be acc_in, and in the last stage
+// acc is psi itself: a thread reads and writes only its own elements of an aliased buffer.  v is aliased with nothing
+// that is written.  Grid and LDS as lvc_stage_driven_kernel.
+template <int NEL>
+__global__ __launch_bounds__(LVC_TILE) void lvc_stage_rk4_kernel(LvcDev m, LvcDrive dr, const c128* __restrict__ Hel,
+                                                                 const c128* __restrict__ W, const c128* __restrict__ A,
+                                                                 const c128* __restrict__ f, const c128* v_g,
+                                                                 const c128* base_g, const c128* acc_in_g, c128* out_g,
+                                                                 c128* acc_g, double c_out, double c_acc) {
+  extern __shared__ __attribute__((aligned(16))) char lvc_smem[];
+  c128* tab = (c128*)lvc_smem;
+  lvc_load_tables_driven(tab, Hel, W, A, dr, f, NEL, m.M);
+  __syncthreads();
+  const int n = blockIdx.x * LVC_TILE + threadIdx.x;
+  if (n >= m.nvib) return;
+  const size_t off = (size_t)blockIdx.y * m.D;
+  const c128* vin = v_g + off;
+  const size_t nvib = m.nvib;
+  c128 v[NEL], y[NEL];
+  lvc_point<NEL>(m, tab, n, [&](int b, int idx) { return vin[b * nvib + idx]; }, v, y);
+#pragma unroll
+  for (int a = 0; a < NEL; ++a) {
+    const size_t e = off + a * nvib + n;
+    const c128 k = cmulmi(y[a]);
+    const c128 ai = acc_in_g[e];
+    if (out_g) out_g[e] = cadd(base_g[e], cscale(k, c_out));
+    acc_g[e] = cadd(ai, cscale(k, c_acc));
+  }
+}
+
+// The whole qd_lvc_driven_rk4 call of member blockIdx.x: lvc_resident_kernel with the tables rebuilt in LDS from the
+// base tables and the drive matrices (both copied to LDS once) whenever the field row changes, a barrier on each side
+// of every rebuild.  grid (B), LVC_RES_TPB threads, dynamic LDS as LvcDrivePlan::lds_* lay it out.
+//   SAMPLE 0 (hold): step s takes row s / hold (rebuilt when s % hold == 0); the Horner step of lvc_resident_kernel.
+//   SAMPLE 1 (stage): classical RK4, the stages of step s take rows 2s, 2s + 1, 2s + 1, 2s + 2: rebuilt before stage 1
+//   and before stage 3 (whose row is the next step's first), and once before the first step.  The stage vectors
+//   ping-pong as in the Horner step (A -> B -> A -> B -> A); k1 .. k4 are summed into registers next to base:
+//   acc = base + dt/6 k1 + dt/3 k2 + dt/3 k3, psi' = acc + dt/6 k4.
+template <int NEL, int SAMPLE>
+__global__ __launch_bounds__(LVC_RES_TPB) void lvc_resident_driven_kernel(
+    LvcDev m, LvcDrive dr, LvcDriveLds L, const c128* __restrict__ Hel, const c128* __restrict__ W,
+    const c128* __restrict__ Adrv, const c128* __restrict__ fvals, int hold, c128* psi_g, double dt, int nsteps,
+    int save_every, int nsave, c128* __restrict__ snap, double* __restrict__ obs, int nobs) {
+  constexpr int KP = (int)((((LVC_DRIVE_RESIDENT_MAX_D + NEL - 1) / NEL) + LVC_RES_TPB - 1) / LVC_RES_TPB);
+  extern __shared__ __attribute__((aligned(16))) char lvc_smem[];
+  c128* A = (c128*)lvc_smem;
+  c128* Bv = (c128*)(lvc_smem + L.vec1);
+  c128* tab0 = (c128*)(lvc_smem + L.tab);
+  c128* tab = (c128*)(lvc_smem + L.eff);
+  c128* drv = (c128*)(lvc_smem + L.drv);
+  double* sh_wave = (double*)(lvc_smem + L.wave);
+  double* sh_tile = (double*)(lvc_smem + L.tile);
+  double* sh_nb = (double*)(lvc_smem + L.nbar);
+  const size_t nvib = m.nvib;
+  constexpr int NN = NEL * NEL;
+  c128* psi = psi_g + (size_t)blockIdx.x * m.D;
+  double* orec = obs ? obs + (size_t)blockIdx.x * (nsave + 1) * nobs * 2 : nullptr;
+  lvc_load_tables(tab0, Hel, W, NEL, m.M);
+  for (int e = threadIdx.x; e < dr.nd * NN; e += blockDim.x) drv[e] = Adrv[e];
+  // the tables of row `row`; every thread calls it
+  auto rebuild = [&](int row) {
+    __syncthreads();
+    lvc_load_tables_driven(tab, tab0, tab0 + NN, drv, dr, fvals + (size_t)row * dr.nd, NEL, m.M);
+    __syncthreads();
+  };
+  c128 base[KP][NEL];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const int n = threadIdx.x + k * LVC_RES_TPB;
+#pragma unroll
+    for (int a = 0; a < NEL; ++a) {
+      base[k][a] = n < m.nvib ? psi[a * nvib + n] : cmk(0, 0);
+      if (n < m.nvib) A[a * nvib + n] = base[k][a];
+    }
+  }
+  __syncthreads();
+  if (orec) lvc_obs_resident(m, A, sh_wave, sh_tile, sh_nb, orec);
+  if (SAMPLE == 1 && nsteps > 0) rebuild(0);
+  for (int s = 0; s < nsteps; ++s) {
+    if (SAMPLE == 0 && s % hold == 0) rebuild(s / hold);
+    c128 acc[SAMPLE == 1 ? KP : 1][NEL];
+#pragma unroll
+    for (int stage = 0; stage < 4; ++stage) {
+      if (SAMPLE == 1 && (stage & 1)) rebuild(2 * s + (stage + 1) / 2);
+      const c128* src = (stage & 1) ? Bv : A;
+      c128* dst = (stage & 1) ? A : Bv;
+      const double coef = SAMPLE == 1 ? (stage == 2 ? dt : stage == 3 ? dt / 6.0 : dt * 0.5) : rk4_horner_coef(dt, stage);
+      const double cacc = stage == 0 ? dt / 6.0 : dt / 3.0;
+#pragma unroll
+      for (int k = 0; k < KP; ++k) {
+        const int n = threadIdx.x + k * LVC_RES_TPB;
+        if (n < m.nvib) {
+          c128 v[NEL], y[NEL];
+          lvc_point<NEL>(m, tab, n, [&](int b, int idx) { return src[b * nvib + idx]; }, v, y);
+#pragma unroll
+          for (int a = 0; a < NEL; ++a) {
+            if constexpr (SAMPLE == 1) {
+              const c128 kk = cmulmi(y[a]);
+              const c128 o = cadd(stage == 3 ? acc[k][a] : base[k][a], cscale(kk, coef));
+              if (stage < 3) acc[k][a] = cadd(stage == 0 ? base[k][a] : acc[k][a], cscale(kk, cacc));
+              dst[a * nvib + n] = o;
+              if (stage == 3) base[k][a] = o;
+            } else {
+              const c128 o = cadd(base[k][a], cscale(cmulmi(y[a]), coef));
+              dst[a * nvib + n] = o;
+              if (stage == 3) base[k][a] = o;
+            }
           }
         }
       }

@@ -1,6 +1,7 @@
 // lvc_plan.hpp — the shape decisions of the linear-vibronic-coupling entry points (lvc.hip: qd_lvc_apply, qd_lvc_rk4,
-// qd_lvc_observe) in plain C++17, no HIP, so that a host build can enumerate them (tools/cpu_emu/lvc_plan_c.cpp,
-// tests/test_lvc_plan_host.py): what a call admits and every refusal with its message, the path (resident or staged),
+// qd_lvc_observe, and qd_lvc_driven_rk4 in the second half: LvcDrivePlan) in plain C++17, no HIP, so that a host build
+// can enumerate them (tools/cpu_emu/lvc_plan_c.cpp, lvc_drive_plan_c.cpp, tests/test_lvc_plan_host.py,
+// test_lvc_drive_plan_host.py): what a call admits and every refusal with its message, the path (resident or staged),
 // the tile, the grids, the LDS bytes and layout of the resident kernel, the scratch layout, and the layout of the
 // observable partials.  lvc.hip executes what lvc_plan returns and decides nothing itself; lvc_kernels.hpp reads the
 // same constants.
@@ -141,6 +142,111 @@ inline LvcPlan lvc_plan(const char* fn, long B, int nel, int M, const int* dims,
   p.ws_part = 2 * p.ws_x1;
   p.ws_part_bytes = lvc_align16((size_t)B * p.rows * p.G * LVC_OBS_NV * 8);
   p.ws_total = p.ws_part + p.ws_part_bytes;
+  return p;
+}
+
+// ---------------------------------------------------------------- laser-driven runs (qd_lvc_driven_rk4)
+// H(t) = H0 - sum_d f_d(t) mu_d with mu_d = A_d (x) 1 (drive_mode -1) or A_d (x) x_j (drive_mode j) is an LVC
+// Hamiltonian with the tables Hel - sum f_d A_d and W[j] - sum f_d A_d: the kernels rebuild their tables from one row
+// of fvals [nf][nd] and run the same stencil.  sample 0 (hold): step s takes row s / hold, the generator is constant
+// within a step and the step is the Horner form of qd_lvc_rk4.  sample 1 (stage): classical RK4, row h holds
+// f(t0 + h dt / 2), the stages of step s take the rows 2s, 2s + 1, 2s + 1, 2s + 2.
+constexpr int LVC_MAX_DRIVES = 8;
+// The driven resident kernel is sized for D <= 2048 (registers: LVC_DRIVE_RESIDENT_MAX_D / NEL / LVC_RES_TPB points per
+// thread; LDS below), and up to there it wins in one to five modes.  nel = 3, one electronic drive, us per step
+// resident / staged in hold mode (tools/bench_lvc.py --driven --scan, profiles/lvc/crossover_scan_driven*.jsonl):
+// M = 1: 7.6 / 14.8 at D = 2046; M = 2: 11.8 / 17.2 at 2028; M = 3: 16.4 / 19.2 at 1944; M = 4: 20.6 / 22.9 at 1875;
+// M = 5: 18.0 / 23.9 at 1536, then a tie within 4 % (25.0 / 25.5 at 1620, 25.1 / 24.4 at 1944; stage mode 25.4 / 27.0).
+// In six modes the step from one to two points per thread (nvib > 512) costs more than the staged launches:
+// 21.0 / 26.5 at 1536, 29.3 / 28.4 at 1584, 29.0 / 27.6 at 1728, 29.3 / 26.9 at 1944, so the limit there is 1536.
+constexpr long LVC_DRIVE_RESIDENT_MAX_D = 2048;
+constexpr long LVC_DRIVE_RESIDENT_MAX_D_M6 = 1536;
+constexpr long lvc_drive_resident_limit(int M) {
+  return M >= 6 ? LVC_DRIVE_RESIDENT_MAX_D_M6 : LVC_DRIVE_RESIDENT_MAX_D;
+}
+// What the driven resident kernel may ask for: two state vectors of 32 KiB at the limit, the base tables, the effective
+// tables and the drive matrices (7 + 7 + 8 KiB at nel = 8, M = 6), the partials.  One workgroup per CU either way.
+constexpr size_t LVC_DRIVE_LDS_MAX = 96 * 1024;
+
+enum LvcSample { LVC_HOLD = 0, LVC_STAGE = 1 };
+
+// The drives as the kernels take them (a kernel argument by value, as LvcDev)
+struct LvcDrive {
+  int nd;
+  int mode[LVC_MAX_DRIVES];   // -1: the table Hel, j: the table W[j]
+};
+
+struct LvcDrivePlan {
+  int refused;   // then only msg is set
+  LvcPlan base;  // lvc_plan() of the same shape with the driven limit's path: dev, the stage, observable and snapshot
+                 // launches, and the scratch of the two stage vectors and the partials
+  LvcDrive drive;
+  int sample, hold;
+  int rows_needed;      // rows of fvals the call reads: ceil(nsteps / hold), or 2 nsteps + 1; 0 when nd = 0
+  LvcLaunch resident;   // the driven resident kernel: grid (B)
+  // its LDS in bytes from the 16-byte aligned base: two stage vectors | base Hel and W | effective Hel and W |
+  // drive matrices | wave partials | tile partials | the nbar parts of the rows
+  size_t lds_vec1, lds_tab, lds_eff, lds_drv, lds_wave, lds_tile, lds_nbar;
+  // scratch in bytes: base.ws_total, then in stage mode the accumulator of B states
+  size_t ws_acc, ws_total;
+  char msg[200];
+};
+
+// The row of fvals that stage `stage` of step `s` reads
+inline long lvc_drive_row(int sample, int hold, long s, int stage) {
+  return sample == LVC_STAGE ? 2 * s + (stage + 1) / 2 : s / hold;
+}
+
+// What qd_lvc_driven_rk4 admits beyond lvc_plan(), and what it launches.  nf is the number of rows fvals holds.
+inline LvcDrivePlan lvc_drive_plan(const char* fn, long B, int nel, int M, const int* dims, int nd,
+                                   const int* drive_mode, int sample, int hold, long nf, int path_req, int nsteps,
+                                   int save_every, bool want_obs) {
+  LvcDrivePlan p{};
+  p.refused = 1;
+  auto refuse = [&](auto... a) {
+    std::snprintf(p.msg, sizeof p.msg, a...);
+    return p;
+  };
+  // the shape, with the path left open: the driven limit decides it below
+  p.base = lvc_plan(fn, B, nel, M, dims, path_req == LVC_RESIDENT ? LVC_AUTO : path_req, nsteps, save_every, want_obs);
+  if (p.base.refused) return refuse("%s", p.base.msg);
+  if (!(nd >= 0 && nd <= LVC_MAX_DRIVES)) return refuse("%s: nd=%d outside [0, %d]", fn, nd, LVC_MAX_DRIVES);
+  if (nd > 0 && !drive_mode) return refuse("%s: null drive_mode", fn);
+  for (int d = 0; d < nd; ++d)
+    if (!(drive_mode[d] >= -1 && drive_mode[d] < M))
+      return refuse("%s: drive_mode[%d]=%d outside [-1, %d)", fn, d, drive_mode[d], M);
+  if (!(sample == LVC_HOLD || sample == LVC_STAGE)) return refuse("%s: sample=%d outside {0, 1}", fn, sample);
+  if (sample == LVC_HOLD && !(hold >= 1)) return refuse("%s: hold=%d must be at least 1", fn, hold);
+  const long need = nd == 0 || nsteps == 0 ? 0 : sample == LVC_STAGE ? 2L * nsteps + 1 : lvc_ceil(nsteps, hold);
+  if (nf < need)
+    return refuse("%s: fvals holds %ld rows, %ld are needed (%s)", fn, nf, need,
+                  sample == LVC_STAGE ? "2 nsteps + 1" : "ceil(nsteps / hold)");
+  const long D = p.base.dev.D;
+  const long limit = lvc_drive_resident_limit(M);
+  const bool fits = D <= limit;
+  if (path_req == LVC_RESIDENT && !fits)
+    return refuse("%s: the resident path needs D <= %ld with %d modes (D = %ld)", fn, limit, M, D);
+  p.refused = 0;
+  p.base.path = path_req == LVC_AUTO ? (fits ? LVC_RESIDENT : LVC_STAGED) : path_req;
+  p.drive.nd = nd;
+  for (int d = 0; d < LVC_MAX_DRIVES; ++d) p.drive.mode[d] = d < nd ? drive_mode[d] : -1;
+  p.sample = sample;
+  p.hold = sample == LVC_HOLD ? hold : 1;
+  p.rows_needed = (int)need;
+
+  if (fits) {
+    const size_t tab = (size_t)(1 + M) * nel * nel * 16;
+    p.lds_vec1 = (size_t)D * 16;
+    p.lds_tab = 2 * p.lds_vec1;
+    p.lds_eff = p.lds_tab + tab;
+    p.lds_drv = p.lds_eff + tab;
+    p.lds_wave = p.lds_drv + (size_t)nd * nel * nel * 16;
+    p.lds_tile = p.lds_wave + lvc_align16((size_t)(LVC_RES_TPB / 64) * LVC_OBS_NV * 8);
+    p.lds_nbar = p.lds_tile + lvc_align16((size_t)lvc_ceil(LVC_DRIVE_RESIDENT_MAX_D, LVC_TILE) * LVC_OBS_NV * 8);
+    p.resident = LvcLaunch{(unsigned)B, 1, 1, LVC_RES_TPB, p.lds_nbar + lvc_align16((size_t)M * nel * 8)};
+  }
+  p.ws_acc = p.base.ws_total;
+  p.ws_total = p.ws_acc + (sample == LVC_STAGE ? (size_t)B * D * 16 : 0);
   return p;
 }
 

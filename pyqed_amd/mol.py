@@ -524,6 +524,45 @@ def lvc_rk4(psi, nel, dims, omega, Hel, W, dt, nsteps, save_every=0, store=True,
     return snap, obs
 
 
+LVC_SAMPLES = {"hold": 0, "stage": 1}
+
+
+def lvc_driven_rk4(psi, nel, dims, omega, Hel, W, A, modes, fvals, dt, nsteps, hold=1, sample="hold", save_every=0,
+                   store=True, observe=True, path="auto", snap=None, obs=None):
+    """Laser-driven lvc_rk4 (qd_lvc_driven_rk4): H(t) = H0 - sum_d f_d(t) A_d (x) (1 | x_j).  A [nd, nel, nel] and fvals
+    [nf, nd] torch complex128 on psi's device (None with no drive), modes [nd] host integers, -1 (or None) for A (x) 1 and
+    j for A (x) x_j.  sample "hold": step s takes row s // hold of fvals (the Horner step of lvc_rk4); "stage": classical
+    RK4, row h is f(t0 + h dt / 2) and step s takes rows 2s, 2s + 1, 2s + 2.  fvals is read when the kernels run: the
+    call is asynchronous.  Everything else as lvc_rk4."""
+    import torch
+    from . import _lib
+    if sample not in LVC_SAMPLES:
+        raise ValueError(f"lvc_driven_rk4: sample={sample!r}, expected 'hold' or 'stage'")
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d, w = _lvc_arrays(dims, omega)
+    md = np.ascontiguousarray(np.array([-1 if k is None else int(k) for k in ([] if modes is None else modes)],
+                                       dtype=np.intc))
+    nd = md.size
+    if nd and (A is None or fvals is None or A.shape[0] != nd or fvals.shape[-1] != nd):
+        raise ValueError(f"lvc_driven_rk4: {nd} drive modes need A [{nd}, nel, nel] and fvals [nf, {nd}]")
+    B = psi.shape[0]
+    nsave = nsteps // save_every if save_every > 0 else 0
+    if snap is None and store and nsave:
+        snap = torch.empty((B, nsave, psi.shape[1]), dtype=torch.complex128, device=dev)
+    if obs is None and observe:
+        obs = torch.empty((B, nsave + 1, lvc_nobs(int(nel), d.size)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_driven_rk4(_lib.ptr(psi), B, int(nel), d.size, d.ctypes.data, w.ctypes.data,
+                                           _lib.ptr(Hel), _lib.ptr(W), nd, _lib.ptr(A) if nd else None,
+                                           md.ctypes.data if nd else None, _lib.ptr(fvals) if nd else None,
+                                           int(fvals.shape[0]) if nd else 0, LVC_SAMPLES[sample], int(hold), float(dt),
+                                           int(nsteps), int(save_every), _lib.ptr(snap), _lib.ptr(obs),
+                                           LVC_PATHS[path], _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_driven_rk4")
+    return snap, obs
+
+
 def lvc_observe(psi, nel, dims):
     """The observable records [B, nobs] of the states psi [B, D] (qd_lvc_observe): rho [nel, nel], X[j] [nel, nel] for
     every mode, nbar [M]."""
@@ -820,12 +859,66 @@ class LVCSolver(SESolver):
     def H(self, value):
         self._H = value
 
+    def _drives(self, edip, pulse):
+        """The drives of a matrix-free pulsed run: (A [nd, nel, nel], modes [nd], field) with field(t) the nd values
+        f_d(t), or None where edip is a D x D matrix (or [D, D, nc]), which SESolver.run takes on the sparse H."""
+        from ._util import issparse, to_numpy
+        m = self.model
+        if edip is None:
+            raise ValueError('Electric dipole must be provided for laser-driven dynamics.')
+
+        def factor(mu, what):
+            """(A [nel, nel], mode) of one dipole, None for a D x D matrix"""
+            if isinstance(mu, LVCOp):
+                if mu.dims != tuple(m.fock_dims) or mu.nel != m.nel:
+                    raise ValueError(f"{what} is an LVCOp of another space than the model's")
+                return mu.A, -1 if mu.mode is None else int(mu.mode)
+            shape = tuple(mu.shape) if hasattr(mu, "shape") else np.shape(mu)
+            if shape[:2] == (m.dim, m.dim) or issparse(mu):
+                return None
+            if shape != (m.nel, m.nel):
+                raise ValueError(f"{what} has shape {shape}: expected an LVCOp, [{m.nel}, {m.nel}] or "
+                                 f"[{m.dim}, {m.dim}]")
+            return to_numpy(mu, np.complex128), -1
+
+        if isinstance(pulse, (list, tuple)):
+            if not isinstance(edip, (list, tuple)) or len(edip) != len(pulse):
+                raise ValueError("a list of pulses needs a list of as many dipoles")
+            fac = [factor(mu, f"edip[{i}]") for i, mu in enumerate(edip)]
+            if any(f is None for f in fac):
+                return None
+            fields = [p.efield for p in pulse]
+            return (np.array([f[0] for f in fac], dtype=complex).reshape(-1, m.nel, m.nel), [f[1] for f in fac],
+                    lambda t: [complex(f(t)) for f in fields])
+        if not isinstance(edip, LVCOp) and not issparse(edip) and np.ndim(edip) == 3:
+            shape = np.shape(edip)
+            if shape[:2] == (m.dim, m.dim):
+                return None
+            if shape[:2] != (m.nel, m.nel):
+                raise ValueError(f"edip has shape {shape}: expected [{m.nel}, {m.nel}, nc] or [{m.dim}, {m.dim}, nc]")
+            nc = shape[2]
+            A = np.ascontiguousarray(np.moveaxis(to_numpy(edip, np.complex128), 2, 0))
+            return A, [-1] * nc, lambda t: np.asarray(pulse.E(t), dtype=complex).reshape(nc)
+        fac = factor(edip, "edip")
+        if fac is None:
+            return None
+        return fac[0].reshape(1, m.nel, m.nel), [fac[1]], lambda t: [complex(pulse.efield(t))]
+
     def run_batch(self, psi0s, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, store_states=True, device=None,
-                  path="auto"):
-        """run() for the rows of psi0s [B, D] in one call: a list of B results."""
+                  path="auto", edip=None, pulse=None, sample="hold"):
+        """run() for the rows of psi0s [B, D] in one call: a list of B results.  With a pulse every member sees the
+        same field (edip as in run(): an LVCOp, [nel, nel], a list of those with a list of pulses, or [nel, nel, nc]
+        with a vector pulse; a D x D dipole is not taken here)."""
         import torch
         from ._util import default_device, issparse, to_numpy
         m = self.model
+        drives = None
+        if pulse is not None:
+            if sample not in LVC_SAMPLES:
+                raise ValueError(f"sample={sample!r}, expected 'hold' or 'stage'")
+            drives = self._drives(edip, pulse)
+            if drives is None:
+                raise ValueError("run_batch: a D x D dipole has no matrix-free form; pass an LVCOp or [nel, nel] factors")
         e_ops = [] if e_ops is None else list(e_ops)
         for i, op in enumerate(e_ops):
             if isinstance(op, LVCOp):
@@ -846,8 +939,19 @@ class LVCSolver(SESolver):
         psi = torch.from_numpy(np.ascontiguousarray(p0).copy()).to(dev)
         Hel = torch.from_numpy(np.ascontiguousarray(m.Hel())).to(dev)
         W = torch.from_numpy(np.ascontiguousarray(m.Wmats())).to(dev)
-        snap, obs = lvc_rk4(psi, m.nel, m.fock_dims, m.omegas, Hel, W, dt, nsteps, save_every=nout, store=store_states,
-                            path=path)
+        if drives is None:
+            snap, obs = lvc_rk4(psi, m.nel, m.fock_dims, m.omegas, Hel, W, dt, nsteps, save_every=nout,
+                                store=store_states, path=path)
+        else:
+            # driven_dynamics' rule: block k of nout steps holds f(t0 + k nout dt); stage mode samples the half-step grid
+            A, modes, field = drives
+            ts = t0 + 0.5 * dt * np.arange(2 * nsteps + 1) if sample == "stage" else \
+                t0 + nout * dt * np.arange(max(nblk - 1, 0))
+            fv = np.array([field(t) for t in ts], dtype=np.complex128).reshape(len(ts), len(modes))
+            snap, obs = lvc_driven_rk4(psi, m.nel, m.fock_dims, m.omegas, Hel, W,
+                                       torch.from_numpy(np.ascontiguousarray(A)).to(dev), modes,
+                                       torch.from_numpy(fv).to(dev), dt, nsteps, hold=nout, sample=sample,
+                                       save_every=nout, store=store_states, path=path)
         rec = obs.cpu().numpy()[:, :nblk]
         nn, M = m.nel * m.nel, m.nmodes
         rho = rec[..., :nn].reshape(B, -1, m.nel, m.nel)
@@ -877,20 +981,32 @@ class LVCSolver(SESolver):
         return results
 
     def run(self, psi0=None, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, store_states=True, device=None, edip=None,
-            pulse=None, use_sparse=True, path="auto"):
+            pulse=None, use_sparse=True, path="auto", sample="hold"):
         """mol.py:1392-1459 with _quantum_dynamics's counts: (Nt//nout - 1) * nout steps, psilist = [psi0] + the state
         after every nout steps, observables (Nt//nout, n_e).  LVCOp e_ops come from the on-device record, any other
         matrix is applied on the host to the stored states.  result.rdm_el [Nt//nout, nel, nel], result.x and
-        result.nbar [Nt//nout, M] come with every run.  store_states=False keeps and copies no state.  With a pulse the
-        run falls through to SESolver.run on self.H."""
+        result.nbar [Nt//nout, M] come with every run.  store_states=False keeps and copies no state.
+
+        With a pulse the run stays matrix-free (qd_lvc_driven_rk4) where edip is held as factors: an LVCOp of the
+        model's space (A (x) 1 or A (x) x_j), an [nel, nel] array (A (x) 1), a list of those with a list of pulses, or
+        an [nel, nel, nc] array with one pulse whose E(t) returns nc components.  Steps and times are driven_dynamics':
+        sample="hold" holds f(t0 + k nout dt) over block k of nout steps; sample="stage" is classical RK4 with the field
+        at the stage times.  The result has the form above (dense psilist, psi the final state).  A D x D edip falls
+        through to SESolver.run on self.H."""
         if psi0 is None:
             psi0 = self.groundstate
         if pulse is not None:
-            e_host = None if e_ops is None else [op.tocsr() if isinstance(op, LVCOp) else op for op in e_ops]
-            return SESolver.run(self, psi0=psi0, dt=dt, Nt=Nt, e_ops=e_host, nout=nout, t0=t0, edip=edip, pulse=pulse,
-                                use_sparse=use_sparse)
+            if sample not in LVC_SAMPLES:
+                raise ValueError(f"sample={sample!r}, expected 'hold' or 'stage'")
+            if self._drives(edip, pulse) is None:
+                if sample != "hold":
+                    raise ValueError(f"sample={sample!r} needs the dipole as factors (an LVCOp or [nel, nel]): a D x D "
+                                     "edip runs on SESolver.run, which holds the field per block")
+                e_host = None if e_ops is None else [op.tocsr() if isinstance(op, LVCOp) else op for op in e_ops]
+                return SESolver.run(self, psi0=psi0, dt=dt, Nt=Nt, e_ops=e_host, nout=nout, t0=t0, edip=edip,
+                                    pulse=pulse, use_sparse=use_sparse)
         p0 = np.asarray(psi0.toarray() if hasattr(psi0, "toarray") else psi0, dtype=complex).reshape(1, -1)
         result = self.run_batch(p0, dt=dt, Nt=Nt, e_ops=e_ops, nout=nout, t0=t0, store_states=store_states,
-                                device=device, path=path)[0]
+                                device=device, path=path, edip=edip, pulse=pulse, sample=sample)[0]
         result.psi0 = psi0
         return result

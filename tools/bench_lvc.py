@@ -8,6 +8,11 @@ One JSON line per (shape, path): the median, minimum and maximum over --repeats 
 4 * 3 * 16 B * D / t: four stages, each at least reading v and psi and writing out once.
 
     python tools/bench_lvc.py [--repeats 5] [--window 0.3] [--out profiles/lvc/bench_lvc.jsonl]
+
+--driven times the laser-driven qd_lvc_driven_rk4 instead (one electronic drive, hold mode with hold = 1 and stage mode,
+each admitted path) next to the undriven qd_lvc_rk4 on the same model and path, whose ratio is the line's
+`vs_undriven`; --scan replaces the shape list by the models between D = 960 and 2046 in one to six modes, for the
+driven resident / staged crossover.  Stage mode moves 16 state streams per step where the Horner step moves 12.
 """
 from __future__ import annotations
 
@@ -24,7 +29,12 @@ sys.path.insert(0, ROOT)
 SHAPES = [(3, (16, 16)), (3, (24, 24, 24)), (3, (16, 16, 16, 16)), (3, (32, 32, 32, 32)), (3, (20, 20, 20, 20, 20)),
           # next to the resident limit (lvc_plan.hpp LVC_RESIDENT_MAX_D) in one, two, four and six modes
           (3, (682,)), (3, (26, 26)), (3, (5, 5, 5, 5)), (3, (3, 3, 3, 3, 3, 2)), (3, (37, 37))]
+# resident against staged below the resident limit, one to six modes (--scan)
+SCAN = [(3, (342,)), (3, (512,)), (3, (682,)), (3, (18, 19)), (3, (22, 23)), (3, (26, 26)), (3, (7, 7, 7)),
+        (3, (8, 8, 8)), (3, (8, 9, 9)), (3, (4, 4, 4, 5)), (3, (5, 5, 5, 5)), (3, (3, 3, 3, 3, 3, 2)),
+        (3, (3, 3, 3, 3, 4, 2))]
 DENSE_MAX_D = 8192
+MAX_STEPS = 50000
 
 
 def model(nel, dims, seed=0):
@@ -67,7 +77,7 @@ def measure(torch, fn, window, repeats):
     fn(2)                                   # warm-up: code objects, scratch
     torch.cuda.synchronize()
     t = time_call(torch, fn, 8)
-    steps = int(min(max(window / max(t, 1e-9), 8), 50000))
+    steps = int(min(max(window / max(t, 1e-9), 8), MAX_STEPS))
     ts = [time_call(torch, fn, steps) for _ in range(repeats)]
     return steps, float(np.median(ts)), float(min(ts)), float(max(ts))
 
@@ -78,17 +88,23 @@ def main():
     ap.add_argument("--window", type=float, default=0.3, help="seconds of work per timed call")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--shapes", default=None, help='e.g. "16,16;24,24,24" (nel = 3)')
+    ap.add_argument("--driven", action="store_true", help="time qd_lvc_driven_rk4 against qd_lvc_rk4")
+    ap.add_argument("--scan", action="store_true", help="the crossover scan's shapes instead of the default list")
     args = ap.parse_args()
     import torch
     from pyqed_amd import _lib
-    from pyqed_amd.mol import lvc_rk4, tdse_rk4
+    from pyqed_amd.mol import lvc_driven_rk4, lvc_rk4, tdse_rk4
     if not torch.cuda.is_available():
         raise SystemExit("bench_lvc needs a GPU: no timing is taken on a CPU")
     dev = torch.device("cuda", 0)
-    shapes = SHAPES if args.shapes is None else [(3, tuple(int(v) for v in s.split(","))) for s in
+    shapes = (SCAN if args.scan else SHAPES) if args.shapes is None else [(3, tuple(int(v) for v in s.split(","))) for s in
                                                  args.shapes.split(";")]
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
     lines = []
+    if args.driven:
+        # one electronic drive sigma_x-like on states 0 and 1; a field small against the model (the timing does not
+        # depend on the values); rows enough for the longest call in stage mode
+        fv = torch.full((2 * MAX_STEPS + 1, 1), 0.01, dtype=torch.complex128, device=dev)
     for nel, dims in shapes:
         D = nel * int(np.prod(dims))
         omega, Hel, W = model(nel, dims)
@@ -108,16 +124,32 @@ def main():
                 continue
             _lib.take_path()
             runs.append((f"lvc_{path}", fn))
-        if D <= DENSE_MAX_D:
+            if args.driven:
+                Ad = torch.zeros((1, nel, nel), dtype=torch.complex128, device=dev)
+                Ad[0, 0, 1] = Ad[0, 1, 0] = 1.0
+                for sample in ("hold", "stage"):
+                    psi = psi0.clone()
+
+                    def dfn(steps, psi=psi, path=path, sample=sample, Ad=Ad):
+                        lvc_driven_rk4(psi, nel, dims, omega, Hd, Wd, Ad, [-1], fv, dt, steps, hold=1, sample=sample,
+                                       observe=False, path=path)
+                    runs.append((f"lvc_driven_{path}_{sample}", dfn))
+        if D <= DENSE_MAX_D and not args.driven:
             H = t(dense_h(nel, dims, omega, Hel, W))
             psi = psi0.clone()
             runs.append(("tdse_rk4_dense", lambda steps, psi=psi, H=H: tdse_rk4(H, psi, dt, steps)))
+        undriven = {}
         for name, fn in runs:
             steps, med, lo, hi = measure(torch, fn, args.window, args.repeats)
+            streams = 16 if name.endswith("_stage") else 12
             rec = {"bench": "lvc", "nel": nel, "dims": list(dims), "D": D, "vector_MiB": D * 16 / 2 ** 20,
                    "path": name, "steps": steps, "repeats": args.repeats, "us_per_step": med * 1e6,
                    "us_per_step_min": lo * 1e6, "us_per_step_max": hi * 1e6,
-                   "effective_TBps": 4 * 3 * 16 * D / med / 1e12}
+                   "effective_TBps": streams * 16 * D / med / 1e12}
+            if name.startswith("lvc_driven_"):
+                rec["vs_undriven"] = med / undriven[name.split("_")[2]]
+            elif name.startswith("lvc_"):
+                undriven[name.split("_")[1]] = med
             line = json.dumps(rec)
             print(line, flush=True)
             lines.append(line)
