@@ -552,4 +552,107 @@ __device__ __forceinline__ void cg_dma_herm_d_gemm_h(const CgSeg* segs, const c1
   }
 }
 
+// ---------------------------------------------------------------- k = A B + (A B)^+ in the accumulators (glf_eig_jump_kernel.hpp)
+// For a tile (R, C) above the diagonal,
+//   k_RC = sum_k A[R, k] B[k, C]  +  conj( sum_k B[k, R] A[C, k] )
+// and the second sum is the same K-tile read with the roles swapped: its MFMA A fragment (m = lane & 15, k = lane >> 4)
+// is B[kt + k][R0 + m], the B-image read of cg_dma_ksteps with the column tile set to R0, and its B fragment is
+// A[C0 + n][kt + k], the A-image read with the row tile set to C0.  Both keep the images' conflict-free patterns, and
+// nothing new is staged.  The conjugation is free in the 3-product form: P1 += ar br and P2 += ai bi are the same for
+// conj(a) conj(b), and P3 takes (ar - ai)(br - bi) instead of the sums; cg_dma_finalise is unchanged.
+// Masks over the wave's tiles (bit mi * 4 + nj): FS the tiles that run the first sum, SW (a subset) those that also
+// run the swapped, conjugated sum, DG the tiles of FS on the diagonal (c0[nj] == r0[mi]): a diagonal tile's fragments
+// are its row's, so they are read once.
+constexpr unsigned cg_xh_row(unsigned m, int mi) { return (m >> (mi * 4)) & 15u; }
+constexpr unsigned cg_xh_col(unsigned m, int nj) { return ((m >> nj) | (m >> (4 + nj))) & 1u; }
+constexpr int cg_xh_diag_row(unsigned dg, int nj) { return (dg >> nj) & 1u ? 0 : (dg >> (4 + nj)) & 1u ? 1 : -1; }
+
+// k-steps [Q0, Q1) of one K-tile: cg_dma_ksteps' order (row fragments, then the column fragments two at a time, the
+// hook behind each pair's reads and ahead of its MFMAs), each tile's swapped sum issued behind the pair's first sums so
+// that no MFMA follows the one it depends on.
+template <unsigned FS, unsigned SW, unsigned DG, int Q0, int Q1, class Hook = CgNoHook>
+__device__ __forceinline__ void cg_dma_ksteps_xh(const CgLds<128>& L, int buf, CgAcc3& acc, const int (&r0)[2],
+                                                 const int (&c0)[4], const Hook& hook = Hook()) {
+  static_assert((SW & ~FS) == 0u && (DG & ~FS) == 0u && (DG & SW) == 0u, "SW and DG are disjoint subsets of FS");
+  constexpr int MW = 2, NW = 4;
+  const int lane = threadIdx.x & 63;
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    const int kk = 4 * q;
+    c128 a[MW], br[MW];
+    double sa[MW], sbr[MW], dbr[MW];
+#pragma unroll
+    for (int mi = 0; mi < MW; ++mi) {
+      if (cg_xh_row(FS, mi)) {
+        a[mi] = L.a[buf][cg_dma_a_slot(r0[mi], lr, kk + lk)];
+        sa[mi] = a[mi].re + a[mi].im;
+      }
+      if (cg_xh_row(SW, mi)) {   // the swapped sums' A fragment: B on the wave's row tile
+        br[mi] = L.b[buf][cg_dma_b_slot(kk + lk, r0[mi] + lr)];
+        dbr[mi] = br[mi].re - br[mi].im;
+        if (cg_xh_row(DG, mi)) sbr[mi] = br[mi].re + br[mi].im;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < NW; h += 2) {
+      c128 b[2], ac[2];
+      double sb[2], dac[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int nj = h + j, dm = cg_xh_diag_row(DG, nj);
+        if (cg_xh_col(FS, nj)) {
+          if (dm >= 0 && cg_xh_row(SW, dm)) {
+            b[j] = br[dm];
+            sb[j] = sbr[dm];
+          } else {
+            b[j] = L.b[buf][cg_dma_b_slot(kk + lk, c0[nj] + lr)];
+            sb[j] = b[j].re + b[j].im;
+          }
+        }
+        if (cg_xh_col(SW, nj)) {   // the swapped sums' B fragment: A on the column tile
+          if (dm >= 0) ac[j] = a[dm];
+          else ac[j] = L.a[buf][cg_dma_a_slot(c0[nj], lr, kk + lk)];
+          dac[j] = ac[j].re - ac[j].im;
+        }
+      }
+      hook(2 * q + h / 2);
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (!(FS & (1u << (mi * 4 + nj)))) continue;
+          acc.re[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].re, b[j].re, acc.re[mi][nj], 0, 0, 0);
+        }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (!(FS & (1u << (mi * 4 + nj)))) continue;
+          acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi].im, b[j].im, acc.im[mi][nj], 0, 0, 0);
+          acc.p3[mi * 4 + nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[j], acc.p3[mi * 4 + nj], 0, 0, 0);
+        }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (!(SW & (1u << (mi * 4 + nj)))) continue;
+          acc.re[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(br[mi].re, ac[j].re, acc.re[mi][nj], 0, 0, 0);
+        }
+#pragma unroll
+      for (int mi = 0; mi < MW; ++mi)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int nj = h + j;
+          if (!(SW & (1u << (mi * 4 + nj)))) continue;
+          acc.im[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(br[mi].im, ac[j].im, acc.im[mi][nj], 0, 0, 0);
+          acc.p3[mi * 4 + nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(dbr[mi], dac[j], acc.p3[mi * 4 + nj], 0, 0, 0);
+        }
+    }
+  }
+}
+
 }  // namespace qd

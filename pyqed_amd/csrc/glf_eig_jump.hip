@@ -86,9 +86,10 @@ extern "C" int qd_lindblad_rk4_eig_jump(const qd_c128* mu, const qd_c128* At, co
     int dev = 0, khz = 100000;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
-    // the kernel's slots: 0 the four passes of the two basis changes, 2 the stages' GEMM (prologue and T included),
-    // 5 publishing, base loads and barrier, 3 the update, 4 the observables; slot 1 is not used
-    const char* names[6] = {"basis-changes", nullptr, "gemm", "update", "obs", "lds-pass"};
+    // the kernel's slots: 0 the four passes of the two basis changes, 2 the stages' GEMM (both sums of every tile),
+    // 3 the tail (dagger, update, the next stage's M o v, hand-over and the pass-end barrier), 4 the observables;
+    // slots 1 and 5 are not used
+    const char* names[6] = {"basis-changes", nullptr, "gemm", "tail", "obs", nullptr};
     std::fprintf(stderr, "[qd phase timing] eig_jump N=%d B=%d nsteps=%d, us per step (basis-changes: per call; mean "
                  "over workgroups):", N, B, nsteps);
     for (int q = 0; q < 6; ++q) {

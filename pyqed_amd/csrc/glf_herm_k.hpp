@@ -1,8 +1,9 @@
 // glf_herm_k.hpp — the stage epilogue of the persistent Hermitian kernels at Np = 128 on the Hermitian tile layout
 // (cgemm_dma128.hpp): k = X + X^+ formed in the registers of the wave that owns the upper element, with one trip of
 // the lower elements through LDS and one barrier ahead of the Horner update (HermKL, herm_k_publish, herm_k_update),
-// and the workgroup's observables without a VGPR held across the K loops.  Shared by the Lindblad batch kernel
-// (glf_batch_kernel.hpp) and lindblad_eig_jump_kernel (glf_eig_jump_kernel.hpp), each in a translation unit of its own.
+// and the workgroup's observables without a VGPR held across the K loops.  The Lindblad batch kernel
+// (glf_batch_kernel.hpp) uses all of it; lindblad_eig_jump_kernel (glf_eig_jump_kernel.hpp), which forms k inside its
+// GEMM, takes wave_uniform and the observables.  Each in a translation unit of its own.
 #pragma once
 #include "cgemm_dma128.hpp"
 #include "glf_kernel.hpp"
