@@ -686,6 +686,32 @@ int qd_lvc_driven_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, cons
                       void* stream);
 
 /*
+ * Conical-intersection dynamics in the local diabatic representation, matrix-free
+ * (pyqed/ldr/ldr.py:1564-1611 LDR2.run, 579-625 LDRN.run).  The reference's kinetic factor
+ *   exp_T[p a, q b] = (U(p)^+ U(q))[a, b] prod_d K_d[p_d, q_d]
+ * with U(p) [M][ns] the ns kept adiabatic states at grid point p over M basis states is applied
+ * factorised, never formed: chi[q][mu] = sum_b U[q][mu][b] psi[q][b], one dense mode product
+ * chi <- K_d chi per axis on the f64 MFMAs, psi'[p][a] = expV[p][a] sum_mu conj(U[p][mu][a])
+ * chi[p][mu].  Work O(npts M sum_d n_d), scratch two states and two arrays [B][npts][M].
+ *   psi    [B][n0](n1)(n2)[ns]  initial states, read only (ndim = 1..3, dims [ndim] a host array)
+ *   U      [npts][M][ns]   expV, expVh [npts][ns]   K_d [n_d][n_d], any complex values, d < ndim
+ *   snap   [B][nsteps / nout][npts][ns]
+ * Step structure of the reference: psi * expVh, then nsteps x (kinetic, * expV), a snapshot after
+ * every nout-th * expV (so snapshots sit half a potential step late, as the reference's do); the
+ * steps after the last snapshot and the closing half step change nothing the reference keeps and
+ * are not run.  Every result is in snap; psi is not written.  With nsteps < nout no snapshot is
+ * due: the call checks its arguments, launches nothing, notes no path and snap may be NULL.
+ *   path 0: the plan's choice; 1: the rotations fused into the first and last axis pass
+ *   (needs (16 / M) M >= 12: M <= 8 or 12 <= M <= 16); 2: expand and project kernels of their own.
+ * Limits, QD_EINVAL with a message before any device work: ndim in [1, 3], 1 <= n_d <= 4096,
+ * 1 <= ns <= M <= 32, B >= 1, B npts M < 2^31, nsteps >= 0, nout >= 1, no null pointer that is
+ * needed.  Asynchronous on its stream and capturable.  Paths noted: ldr_axes_fused, ldr_axes_split.
+ */
+int qd_ldr_run(const qd_c128* psi, int B, int ndim, const int* dims, int M, int ns, const qd_c128* U,
+               const qd_c128* expV, const qd_c128* expVh, const qd_c128* K0, const qd_c128* K1,
+               const qd_c128* K2, int nsteps, int nout, qd_c128* snap, int path, void* stream);
+
+/*
  * 3D multi-state split operator (pyqed/wpd.py:1349-1411 SPO3.run, linear KEO
  * _KEO_linear wpd.py:1419-1432 = fftn over axes (0,1,2)).  psi [nx][ny][nz][ns],
  * expVh [nx][ny][nz][ns][ns], expK [nx][ny][nz]; snap [nsteps/nout][...].
