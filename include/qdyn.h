@@ -712,6 +712,27 @@ int qd_ldr_run(const qd_c128* psi, int B, int ndim, const int* dims, int M, int 
                const qd_c128* K2, int nsteps, int nout, qd_c128* snap, int path, void* stream);
 
 /*
+ * qd_ldr_run for a kinetic factor whose propagator along the last axis differs for every row of
+ * the grid but has the same eigenvectors in every row (pyqed/ldr/ldr.py:1779-1987 LDR2_Jacobi:
+ * T = p_r^2 / 2 mu + p_theta^2 / 2 I(r), expTy[i] = S diag(exp(-i E_m dt / I(x_i))) S).  One
+ * kinetic step is
+ *   chi = expand(psi) with U;  chi <- F chi along the last axis, then chi[p] *= ph[p];
+ *   chi <- K_d chi along every axis d < ndim - 1;  chi <- Fb chi along the last axis;
+ *   psi' = expV project(chi) with conj(U)
+ * with the two last-axis passes on a real matrix (two MFMAs per complex k-step, not four).
+ *   F, Fb  [n_last][n_last] real, any values (F = Fb = S for the reference's class)
+ *   ph     [npts], the grid's shape with the index of F's rows in the last axis' place
+ *   K0, K1 [n_d][n_d] for the axes d < ndim - 1; those at or past ndim - 1 are ignored, may be NULL
+ * Everything else (psi, U, expV, expVh, snap, the step structure and the snapshots, path, the
+ * limits and their messages, nsteps < nout) is qd_ldr_run's.  Asynchronous on its stream and
+ * capturable.  Paths noted: ldr_jacobi_fused, ldr_jacobi_split.
+ */
+int qd_ldr_jacobi_run(const qd_c128* psi, int B, int ndim, const int* dims, int M, int ns,
+                      const qd_c128* U, const qd_c128* expV, const qd_c128* expVh, const double* F,
+                      const double* Fb, const qd_c128* ph, const qd_c128* K0, const qd_c128* K1,
+                      int nsteps, int nout, qd_c128* snap, int path, void* stream);
+
+/*
  * 3D multi-state split operator (pyqed/wpd.py:1349-1411 SPO3.run, linear KEO
  * _KEO_linear wpd.py:1419-1432 = fftn over axes (0,1,2)).  psi [nx][ny][nz][ns],
  * expVh [nx][ny][nz][ns][ns], expK [nx][ny][nz]; snap [nsteps/nout][...].

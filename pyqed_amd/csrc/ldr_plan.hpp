@@ -171,4 +171,104 @@ inline LdrPlan ldr_plan(const char* fn, long B, int ndim, const int* dims, int M
   return p;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// qd_ldr_jacobi_run: the kinetic factor of LDR2_Jacobi (pyqed/ldr/ldr.py:1870-1936), whose propagator along the last
+// axis differs for every row of the grid, expTy[i] = S diag(exp(-i E_m dt / I(x_i))) S.  Every row's matrix has the
+// same eigenvectors, so the last axis is passed twice with a real matrix and the rows differ in a table only:
+//     chi  = expand(psi) with U
+//     chi <- F along the last axis, then chi[p] *= ph[p]      real matrix; ph has the grid's shape, mode index last
+//     chi <- K_d along every axis d < ndim - 1                the plain complex pass of ldr_plan
+//     chi <- Fb along the last axis                           real matrix
+//     psi' = expV project(chi) with U^+
+// The pass list is forward (axis ndim - 1), plain (axes 0 .. ndim - 2), back (axis ndim - 1): ndim + 1 passes.  A real
+// pass has the geometry of a plain one (the B tile staged in LDS is complex either way); its A fragments are doubles
+// and it issues two MFMAs per k-step where the plain pass issues four.  Fused path: the forward pass expands on load and
+// multiplies ph on store, the back pass projects on store.  Split path: the point kernels of ldr_plan around the same
+// passes, the forward one still multiplying ph.  What is admitted, every refusal and the scratch layout are ldr_plan's.
+constexpr int LDR_JACOBI_MAX_PASS = LDR_MAX_DIM + 1;
+
+struct LdrJacobiPass {
+  int axis;         // the axis the pass runs along
+  int real;         // the matrix is real (F or Fb): forward and back; 0: the plain ldr_axis_kernel with K[axis]
+  int expand;       // forms chi from psi and U on load (forward, fused)
+  int phase;        // multiplies ph[point block in its member, row] on store (forward)
+  int project;      // projects with conj(U), multiplies expV and stores psi' (back, fused)
+  int n, ktiles, cu;
+  int src, dst;     // LdrBuf
+  unsigned s, st, outer, C;
+  LdrLaunch launch;
+};
+
+struct LdrJacobiPlan {
+  int refused;      // then only msg is set
+  int path;         // LDR_FUSED or LDR_SPLIT
+  int ndim, M, ns, B;
+  int n[LDR_MAX_DIM];
+  long npts;
+  int nsnap, nrun;
+  int npass;        // ndim + 1
+  LdrJacobiPass pass[LDR_JACOBI_MAX_PASS];
+  int expand_dst, project_src;   // split path
+  LdrLaunch open, expand, project;
+  size_t ws_psi0, ws_psi1, ws_w0, ws_w1, ws_total;
+  char msg[200];
+};
+
+inline LdrJacobiPlan ldr_jacobi_plan(const char* fn, long B, int ndim, const int* dims, int M, int ns, int nsteps,
+                                     int nout, int path_req = LDR_AUTO) {
+  LdrJacobiPlan p{};
+  const LdrPlan b = ldr_plan(fn, B, ndim, dims, M, ns, nsteps, nout, path_req);
+  if (b.refused) {
+    p.refused = 1;
+    std::copy(b.msg, b.msg + sizeof b.msg, p.msg);
+    return p;
+  }
+  p.path = b.path;
+  p.ndim = ndim;
+  p.M = M;
+  p.ns = ns;
+  p.B = b.B;
+  p.npts = b.npts;
+  p.nsnap = b.nsnap;
+  p.nrun = b.nrun;
+  for (int d = 0; d < LDR_MAX_DIM; ++d) p.n[d] = b.n[d];
+  const bool fused = p.path == LDR_FUSED;
+  p.npass = ndim + 1;
+  for (int i = 0; i < p.npass; ++i) {
+    LdrJacobiPass& a = p.pass[i];
+    const bool fwd = i == 0, back = i == p.npass - 1;
+    a.axis = fwd || back ? ndim - 1 : i - 1;
+    const LdrAxis& g = b.axis[a.axis];
+    a.real = fwd || back;
+    a.expand = fused && fwd;
+    a.phase = fwd;
+    a.project = fused && back;
+    a.n = g.n;
+    a.ktiles = g.ktiles;
+    a.s = g.s;
+    a.st = g.st;
+    a.outer = g.outer;
+    a.C = g.C;
+    a.cu = a.project ? ldr_fused_cols(M) : LDR_SUB;
+    // fused: psi -> W0 -> W1 -> ... -> psi; split: W0 -> W1 -> W0 ...
+    a.src = a.expand ? LDR_BUF_PSI : (fused ? LDR_BUF_W0 + (i - 1) % 2 : LDR_BUF_W0 + i % 2);
+    a.dst = a.project ? LDR_BUF_PSI : (fused ? LDR_BUF_W0 + i % 2 : LDR_BUF_W0 + (i + 1) % 2);
+    const size_t lds = (size_t)LDR_KT * LDR_BS_STRIDE * 16 +
+                       (a.project ? (size_t)LDR_WAVES * LDR_SUB * LDR_DS_STRIDE * 16 : 0);
+    a.launch = LdrLaunch{(unsigned)ldr_ceil(a.C, (long)LDR_NSUB * a.cu), (unsigned)ldr_ceil(a.n, LDR_RT), 1, LDR_TPB,
+                         lds};
+  }
+  p.expand_dst = LDR_BUF_W0;
+  p.project_src = LDR_BUF_W0 + p.npass % 2;
+  p.open = b.open;
+  p.expand = b.expand;
+  p.project = b.project;
+  p.ws_psi0 = b.ws_psi0;
+  p.ws_psi1 = b.ws_psi1;
+  p.ws_w0 = b.ws_w0;
+  p.ws_w1 = b.ws_w1;
+  p.ws_total = b.ws_total;
+  return p;
+}
+
 }  // namespace qd

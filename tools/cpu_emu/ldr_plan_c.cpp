@@ -17,4 +17,10 @@ void plan_ldr(const char* fn, long B, int ndim, const int* dims, int M, int ns, 
   *out = ldr_plan(fn, B, ndim, dims, M, ns, nsteps, nout, path);
 }
 int plan_ldr_fusable(int M) { return M >= 1 && ldr_fusable(M) ? ldr_fused_cols(M) : 0; }
+// qd_ldr_jacobi_run's plan (tests/test_ldr_jacobi_plan_host.py)
+void plan_ldr_jacobi(const char* fn, long B, int ndim, const int* dims, int M, int ns, int nsteps, int nout, int path,
+                     LdrJacobiPlan* out) {
+  *out = ldr_jacobi_plan(fn, B, ndim, dims, M, ns, nsteps, nout, path);
+}
+int plan_ldr_jacobi_max_pass() { return LDR_JACOBI_MAX_PASS; }
 }

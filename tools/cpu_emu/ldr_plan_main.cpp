@@ -3,6 +3,7 @@
 // Plans every axis length 1 .. 130 and around the longest on every axis of one to three dimensions, the whole
 // 1 <= ns <= M <= 32 square, B in {1, 3, 64, 2^31 - 1}, every path request and out-of-range arguments, and checks what
 // a reader of the plan relies on: tiles cover rows, K and columns, the buffers chain, the scratch parts are disjoint.
+// Every call is planned by ldr_jacobi_plan as well (forward, plain and back passes of qd_ldr_jacobi_run).
 #include <cstdlib>
 #include <cstring>
 
@@ -18,8 +19,37 @@ static void fail(const char* what, const LdrPlan& p) {
   std::exit(1);
 }
 
+static void walk_jacobi(long B, int ndim, const int* dims, int M, int ns, int nsteps, int nout, int path,
+                        const LdrPlan& base) {
+  const LdrJacobiPlan p = ldr_jacobi_plan("ldr_plan_main", B, ndim, dims, M, ns, nsteps, nout, path);
+  if (p.refused != base.refused || std::strcmp(p.msg, base.msg)) fail("jacobi: refusal differs from ldr_plan's", base);
+  if (p.refused) return;
+  const bool fused = p.path == LDR_FUSED;
+  if (p.npass != p.ndim + 1 || p.npass > LDR_JACOBI_MAX_PASS) fail("jacobi: pass count", base);
+  int prev = fused ? (int)LDR_BUF_PSI : p.expand_dst;
+  for (int i = 0; i < p.npass; ++i) {
+    const LdrJacobiPass& a = p.pass[i];
+    const bool end = i == 0 || i == p.npass - 1;
+    if (a.axis != (end ? p.ndim - 1 : i - 1) || a.real != end || a.phase != (i == 0)) fail("jacobi: pass order", base);
+    if (a.real && (a.s != 1 || a.st != (unsigned)p.M || (long)a.outer * a.n != p.npts)) fail("jacobi: real axis", base);
+    if ((long)a.launch.gy * LDR_RT < a.n || (long)(a.launch.gy - 1) * LDR_RT >= a.n) fail("jacobi: row tiles", base);
+    if ((long)a.ktiles * LDR_KT < a.n || (long)(a.ktiles - 1) * LDR_KT >= a.n) fail("jacobi: K-tiles", base);
+    const long per = (long)LDR_NSUB * a.cu;
+    if ((long)a.launch.gx * per < (long)a.C || (long)(a.launch.gx - 1) * per >= (long)a.C)
+      fail("jacobi: column tiles", base);
+    if (a.project && (a.cu % p.M || a.C % p.M)) fail("jacobi: a point straddles sub-tiles", base);
+    if (a.launch.lds > LDR_LDS_MAX) fail("jacobi: LDS", base);
+    if (a.src != prev || a.src == a.dst) fail("jacobi: buffer chain", base);
+    prev = a.dst;
+  }
+  if (prev != (fused ? (int)LDR_BUF_PSI : p.project_src)) fail("jacobi: buffer chain end", base);
+  if (p.ws_psi1 != base.ws_psi1 || p.ws_w0 != base.ws_w0 || p.ws_w1 != base.ws_w1 || p.ws_total != base.ws_total)
+    fail("jacobi: scratch layout differs from ldr_plan's", base);
+}
+
 static void walk(long B, int ndim, const int* dims, int M, int ns, int nsteps, int nout, int path) {
   const LdrPlan p = ldr_plan("ldr_plan_main", B, ndim, dims, M, ns, nsteps, nout, path);
+  walk_jacobi(B, ndim, dims, M, ns, nsteps, nout, path, p);
   if (p.refused) {
     if (std::strlen(p.msg) == 0 || std::strlen(p.msg) >= sizeof p.msg - 1) fail("refusal without a whole message", p);
     ++refusals;
