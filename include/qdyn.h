@@ -686,6 +686,41 @@ int qd_lvc_driven_rk4(qd_c128* psi, int B, int nel, int M, const int* dims, cons
                       void* stream);
 
 /*
+ * Pair records of the LVC model, matrix-free: what a multi-time correlation function
+ * <bra(t)| b |ket(t)> (pyqed/mol.py:1475-1566 SESolver.correlation_3op_1t .. 4op_2t on the LVC H)
+ * reads, with b held as factors.  psi [P][2][D] holds P pairs, the ket then the bra of each, both
+ * of the model above.  Block r of a pair's record is
+ *   R_r[a][b] = sum_n L_r[a,n] conj(bra[b,n]),   L_0 = ket,  L_{j+1} = x_j ket
+ *   <bra| A x 1 |ket> = tr(A R_0),   <bra| A x x_j |ket> = tr(A R_{j+1})
+ * and blocks [nblk] (a host array read at call time, as dims is; entries in [0, M], 1 <= nblk <=
+ * 1 + M) names the blocks a call returns, in that order.  Nothing is derived by conjugation except
+ * the bra factor of the sum.
+ *
+ * qd_lvc_pair_observe: rec [P][nblk][nel][nel], one record per pair.
+ *
+ * qd_lvc_pair_rk4: nsteps steps of both states of every pair in place (the Horner RK4 of
+ *   qd_lvc_rk4 on the 2 P states), one record at t0 and one after every save_every steps:
+ *   rec [P][nsteps/save_every + 1][nblk][nel][nel].  path as for qd_lvc_rk4; the resident path
+ *   runs one workgroup per pair with four stage vectors in LDS, up to the measured crossover:
+ *   D <= 1024 in one and two modes, D <= 768 in three to five, never in six.
+ *
+ * Every sum has an order the shape alone fixes (no atomics, no contraction), the order of
+ * qd_lvc_observe's row (r, a): identical calls agree bit for bit; the in-run records equal
+ * qd_lvc_pair_observe of the same states bit for bit on either path; a block's bits do not depend
+ * on which other blocks are asked for; with bra = ket, block r equals the rho (r = 0) or X[r - 1]
+ * part of qd_lvc_observe's record bit for bit.  Asynchronous on the stream and capturable; scratch
+ * is call-scoped.  QD_EINVAL before any device work, psi unchanged, for: P outside [1, 32767] (the
+ * 2 P states are one batch), nblk outside [1, 1 + M], a blocks entry outside [0, M], a null
+ * pointer (rec included), save_every < 1 with nsteps > 0, and everything qd_lvc_rk4 refuses.
+ * Paths noted: lvc_pair_staged, lvc_pair_resident.
+ */
+int qd_lvc_pair_observe(const qd_c128* psi, int P, int nel, int M, const int* dims, int nblk,
+                        const int* blocks, qd_c128* rec, void* stream);
+int qd_lvc_pair_rk4(qd_c128* psi, int P, int nel, int M, const int* dims, const double* omega,
+                    const qd_c128* Hel, const qd_c128* W, double dt, int nsteps, int save_every,
+                    int nblk, const int* blocks, qd_c128* rec, int path, void* stream);
+
+/*
  * Conical-intersection dynamics in the local diabatic representation, matrix-free
  * (pyqed/ldr/ldr.py:1564-1611 LDR2.run, 579-625 LDRN.run).  The reference's kinetic factor
  *   exp_T[p a, q b] = (U(p)^+ U(q))[a, b] prod_d K_d[p_d, q_d]

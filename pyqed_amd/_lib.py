@@ -139,6 +139,9 @@ SIGNATURES = {
     "qd_lvc_driven_rk4": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p,
                                   c_int, c_void_p]),
+    "qd_lvc_pair_observe": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "qd_lvc_pair_rk4": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int,
+                                c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "qd_ldr_run": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "qd_ldr_jacobi_run": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,

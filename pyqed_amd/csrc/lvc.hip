@@ -1,11 +1,11 @@
-// lvc.hip — linear vibronic coupling in Fock space, matrix-free: qd_lvc_apply, qd_lvc_rk4, qd_lvc_observe and the
-// laser-driven qd_lvc_driven_rk4.
+// lvc.hip — linear vibronic coupling in Fock space, matrix-free: qd_lvc_apply, qd_lvc_rk4, qd_lvc_observe, the
+// laser-driven qd_lvc_driven_rk4, and the pair record and its run, qd_lvc_pair_observe and qd_lvc_pair_rk4.
 //
 // Replaces LVC.buildH + SESolver.run of pyqed/mol.py:959-1262 on a dense or sparse H by the stencil of
 // lvc_kernels.hpp.  This file is the host side only: pointer checks, the plan (lvc_plan.hpp decides what is admitted,
 // the path, every grid and the scratch layout), scratch from the arena, and the launches.  dims and omega are host
 // arrays read at call time into kernel arguments, so the calls are asynchronous and a capture holds their values.
-#include "lvc_kernels.hpp"
+#include "lvc_pair_kernels.hpp"
 
 namespace qd {
 namespace {
@@ -170,6 +170,64 @@ int lvc_launch_resident_driven(const LvcDrivePlan& dp, const LvcDev& m, const Lv
   return QD_OK;
 }
 
+// ---------------------------------------------------------------- pair records
+int lvc_pair_refused(const LvcPairPlan& p) {
+  set_error("%s", p.msg);
+  return QD_EINVAL;
+}
+
+// the records of the P pairs psi [P][2][D] into rec + p * rec_pstride (complex values)
+int lvc_pair_record(const LvcPairPlan& pp, const LvcDev& m, const c128* psi, double* part, c128* rec,
+                    size_t rec_pstride, hipStream_t st) {
+  const bool hit = dispatch_lvc_nel(m.nel, [&](auto N) {
+    hipLaunchKernelGGL((lvc_pair_part_kernel<decltype(N)::value>), grid_of(pp.part), dim3(pp.part.tpb), 0, st, m,
+                       pp.blocks, psi, part);
+    return true;
+  });
+  QD_CHECK_ARG(hit, "lvc: no pair kernel for nel=%d", m.nel);
+  QD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(lvc_pair_final_kernel, grid_of(pp.fin), dim3(pp.fin.tpb), 0, st, m.nel, pp.blocks.nblk, pp.rows,
+                     pp.base.G, (const double*)part, (double*)rec, 2 * rec_pstride);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
+int lvc_run_pair_staged(const LvcPairPlan& pp, const LvcDev& m, const c128* Hel, const c128* W, c128* psi, double dt,
+                        int nsteps, int save_every, int nsave, c128* rec, hipStream_t st) {
+  const LvcPlan& p = pp.base;
+  void* w = nullptr;
+  QD_TRY(workspace(WS_MISC, pp.ws_total, &w, st));
+  c128* x0 = (c128*)((char*)w + p.ws_x0);
+  c128* x1 = (c128*)((char*)w + p.ws_x1);
+  double* part = (double*)((char*)w + pp.ws_part);
+  const size_t rec_p = (size_t)(nsave + 1) * pp.nrec;
+  QD_TRY(lvc_pair_record(pp, m, psi, part, rec, rec_p, st));
+  const double c[4] = {dt * 0.25, dt / 3.0, dt * 0.5, dt};   // rk4_horner_coef
+  for (int s = 0; s < nsteps; ++s) {
+    QD_TRY(lvc_stage(p, m, Hel, W, psi, psi, x0, c[0], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x0, psi, x1, c[1], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x1, psi, x0, c[2], st));
+    QD_TRY(lvc_stage(p, m, Hel, W, x0, psi, psi, c[3], st));
+    if ((s + 1) % save_every == 0)
+      QD_TRY(lvc_pair_record(pp, m, psi, part, rec + (size_t)((s + 1) / save_every) * pp.nrec, rec_p, st));
+  }
+  return QD_OK;
+}
+
+template <int NEL>
+int lvc_launch_resident_pair(const LvcPairPlan& pp, const LvcDev& m, const c128* Hel, const c128* W, c128* psi,
+                             double dt, int nsteps, int save_every, int nsave, c128* rec, hipStream_t st) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)lvc_resident_pair_kernel<NEL>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LVC_LDS_MAX);
+  QD_HIP(attr);
+  const LvcPairLds L{(unsigned)pp.lds_ket1, (unsigned)pp.lds_bra0, (unsigned)pp.lds_bra1,
+                     (unsigned)pp.lds_tab,  (unsigned)pp.lds_wave, (unsigned)pp.lds_tile};
+  hipLaunchKernelGGL((lvc_resident_pair_kernel<NEL>), grid_of(pp.resident), dim3(pp.resident.tpb), pp.resident.lds,
+                     st, m, pp.blocks, L, Hel, W, psi, dt, nsteps, save_every, nsave, (double*)rec, pp.nrec);
+  QD_HIP(hipGetLastError());
+  return QD_OK;
+}
+
 }  // namespace
 }  // namespace qd
 
@@ -258,4 +316,42 @@ extern "C" int qd_lvc_driven_rk4(qd_c128* psi, int B, int nel, int M, const int*
   }
   note_path("lvc_driven_staged");
   return lvc_run_driven_staged(dp, m, t, (c128*)psi, B, dt, nsteps, save_every, nsave, (c128*)snap, (c128*)obs, st);
+}
+
+extern "C" int qd_lvc_pair_observe(const qd_c128* psi, int P, int nel, int M, const int* dims, int nblk,
+                                   const int* blocks, qd_c128* rec, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(psi && rec, "qd_lvc_pair_observe: null pointer");
+  const LvcPairPlan pp = lvc_pair_plan("qd_lvc_pair_observe", P, nel, M, dims, nblk, blocks);
+  if (pp.refused) return lvc_pair_refused(pp);
+  void* w = nullptr;
+  QD_TRY(workspace(WS_MISC, pp.ws_part_bytes, &w, st));
+  return lvc_pair_record(pp, pp.base.dev, (const c128*)psi, (double*)w, (c128*)rec, pp.nrec, st);
+}
+
+extern "C" int qd_lvc_pair_rk4(qd_c128* psi, int P, int nel, int M, const int* dims, const double* omega,
+                               const qd_c128* Hel, const qd_c128* W, double dt, int nsteps, int save_every, int nblk,
+                               const int* blocks, qd_c128* rec, int path, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WsScope wss_(st);  // call-scoped scratch (qd_runtime.hip)
+  QD_CHECK_ARG(psi && omega && Hel && W && rec, "qd_lvc_pair_rk4: null pointer");
+  const LvcPairPlan pp = lvc_pair_plan("qd_lvc_pair_rk4", P, nel, M, dims, nblk, blocks, path, nsteps, save_every);
+  if (pp.refused) return lvc_pair_refused(pp);
+  const LvcDev m = lvc_dev(pp.base, omega);
+  const int nsave = save_every > 0 ? nsteps / save_every : 0;
+  if (pp.base.path == LVC_RESIDENT) {
+    note_path("lvc_pair_resident");
+    int rc = QD_OK;
+    const bool hit = dispatch_lvc_nel(nel, [&](auto N) {
+      rc = lvc_launch_resident_pair<decltype(N)::value>(pp, m, (const c128*)Hel, (const c128*)W, (c128*)psi, dt, nsteps,
+                                                        save_every, nsave, (c128*)rec, st);
+      return true;
+    });
+    QD_CHECK_ARG(hit, "qd_lvc_pair_rk4: no resident kernel for nel=%d", nel);
+    return rc;
+  }
+  note_path("lvc_pair_staged");
+  return lvc_run_pair_staged(pp, m, (const c128*)Hel, (const c128*)W, (c128*)psi, dt, nsteps, save_every, nsave,
+                             (c128*)rec, st);
 }

@@ -1,7 +1,8 @@
 // lvc_plan.hpp — the shape decisions of the linear-vibronic-coupling entry points (lvc.hip: qd_lvc_apply, qd_lvc_rk4,
-// qd_lvc_observe, and qd_lvc_driven_rk4 in the second half: LvcDrivePlan) in plain C++17, no HIP, so that a host build
-// can enumerate them (tools/cpu_emu/lvc_plan_c.cpp, lvc_drive_plan_c.cpp, tests/test_lvc_plan_host.py,
-// test_lvc_drive_plan_host.py): what a call admits and every refusal with its message, the path (resident or staged),
+// qd_lvc_observe, qd_lvc_driven_rk4 in the second part: LvcDrivePlan, and qd_lvc_pair_observe / qd_lvc_pair_rk4 in the
+// third: LvcPairPlan) in plain C++17, no HIP, so that a host build can enumerate them (tools/cpu_emu/lvc_plan_c.cpp,
+// lvc_drive_plan_c.cpp, lvc_pair_plan_c.cpp, tests/test_lvc_plan_host.py, test_lvc_drive_plan_host.py,
+// test_lvc_pair_plan_host.py): what a call admits and every refusal with its message, the path (resident or staged),
 // the tile, the grids, the LDS bytes and layout of the resident kernel, the scratch layout, and the layout of the
 // observable partials.  lvc.hip executes what lvc_plan returns and decides nothing itself; lvc_kernels.hpp reads the
 // same constants.
@@ -247,6 +248,110 @@ inline LvcDrivePlan lvc_drive_plan(const char* fn, long B, int nel, int M, const
   }
   p.ws_acc = p.base.ws_total;
   p.ws_total = p.ws_acc + (sample == LVC_STAGE ? (size_t)B * D * 16 : 0);
+  return p;
+}
+
+// ---------------------------------------------------------------- pair records (qd_lvc_pair_observe, qd_lvc_pair_rk4)
+// P pairs (ket, bra) of one model, psi [P][2][D]: the 2P states are the batch of the stage kernel, and block r of a
+// pair's record is R_r[a][b] = sum_n L_r[a, n] conj(bra[b, n]) with L_0 = ket, L_{j+1} = x_j ket.  A call names the
+// blocks it wants (blocks [nblk], entries in [0, M]); every block is summed on its own, in the order of the
+// observable record's row (r, a), so a subset of blocks has the bits of the all-block call.
+constexpr int LVC_PAIR_MAX = 32767;       // pairs of one call: 2 P states stay within LVC_GRID_YZ_MAX
+constexpr int LVC_PAIR_REG_NEL = 4;       // up to here a thread accumulates all nel^2 sums of a block in one pass
+constexpr int LVC_PAIR_NV_MAX = 2 * LVC_PAIR_REG_NEL * LVC_PAIR_REG_NEL;   // doubles of one partial row at most
+// The pair resident kernel holds four stage vectors (ket A/B, bra A/B) where the single-state one holds two, so it
+// starts at half that kernel's limit: four vectors of 16 KiB, inside LVC_LDS_MAX with the tables and partials (74
+// KiB at nel = 8, M = 6), and 2 ceil(1024 / nel / LVC_RES_TPB) base points per thread, no more registers than the
+// single-state kernel's.  That is what the kernel is built for; the plan goes resident up to the measured crossover of
+// the mode count, as the driven plan does.  nel = 3, one pair, one block, a record every step, us per step resident /
+// staged (tools/bench_lvc.py --pair --scan, profiles/lvc_pair/): M = 1: 12.8 / 21.2 at D = 510, 15.3 / 22.7 at 1023;
+// M = 2: 17.7 / 23.0 at 768, 21.5 / 24.9 at 972; M = 3: 22.2 / 26.5 at 756, 28.1 / 27.2 at 840, 27.8 / 27.7 at 882;
+// M = 4: 26.3 / 28.0 at 768, 33.9 / 29.3 at 960; M = 5: 30.9 / 31.1 at 729, 40.8 / 33.3 at 972; M = 6: 33.9 / 31.3 at
+// 192, 36.6 / 33.1 at 288, 35.5 / 32.6 at 480, 46.6 / 35.6 at 972.  From three modes on the step from one to two
+// points per thread of the record's tile (nvib > 256, D > 768 at nel = 3) is where staged takes over; in six modes the
+// one workgroup never catches the staged launches, so the plan never chooses it there (a forced call is refused).
+constexpr long LVC_PAIR_RESIDENT_MAX_D = LVC_RESIDENT_MAX_D / 2;
+constexpr long LVC_PAIR_RESIDENT_MAX_D_M345 = 768;
+constexpr long lvc_pair_resident_limit(int M) {
+  return M <= 2 ? LVC_PAIR_RESIDENT_MAX_D : M <= 5 ? LVC_PAIR_RESIDENT_MAX_D_M345 : 0;
+}
+
+// The blocks of a call as the kernels take them (a kernel argument by value, as LvcDev)
+struct LvcPairBlocks {
+  int nblk;
+  int r[1 + LVC_MAX_MODES];   // 0: ket, j + 1: x_j ket
+};
+
+struct LvcPairPlan {
+  int refused;   // then only msg is set
+  LvcPlan base;  // lvc_plan() of the 2 P states with the pair limit's path: dev, the stage launch, the two stage vectors
+  int P;
+  LvcPairBlocks blocks;
+  int rows;      // rows a of a block that one pass accumulates: nel (nel <= LVC_PAIR_REG_NEL) or 1
+  int passes;    // nel / rows
+  int nv;        // doubles of one partial row: 2 nel rows (value v: row v / (2 nel), column (v / 2) % nel, re | im)
+  int nrec;      // complex values of one record: nblk nel^2
+  LvcLaunch part;       // grid (base.G, nblk passes, P)
+  LvcLaunch fin;        // grid (P)
+  LvcLaunch resident;   // the whole call: grid (P)
+  // resident LDS in bytes from the 16-byte aligned base: ket A | ket B | bra A | bra B | Hel and W | wave partials |
+  // tile partials
+  size_t lds_ket1, lds_bra0, lds_bra1, lds_tab, lds_wave, lds_tile;
+  // scratch in bytes: the two stage vectors of the 2 P states (base.ws_x0, base.ws_x1), then the partial rows
+  // [P][nblk][passes][G][nv] doubles in the place of the observable partials, which a pair call never takes
+  size_t ws_part, ws_part_bytes, ws_total;   // qd_lvc_pair_observe takes ws_part_bytes alone
+  char msg[200];
+};
+
+// What qd_lvc_pair_observe and qd_lvc_pair_rk4 admit, and what they launch.  path_req, nsteps and save_every matter to
+// qd_lvc_pair_rk4 only (qd_lvc_pair_observe passes LVC_AUTO, 0, 0).
+inline LvcPairPlan lvc_pair_plan(const char* fn, long P, int nel, int M, const int* dims, int nblk, const int* blocks,
+                                 int path_req = LVC_AUTO, int nsteps = 0, int save_every = 0) {
+  LvcPairPlan p{};
+  p.refused = 1;
+  auto refuse = [&](auto... a) {
+    std::snprintf(p.msg, sizeof p.msg, a...);
+    return p;
+  };
+  if (!(P >= 1 && P <= LVC_PAIR_MAX)) return refuse("%s: P=%ld outside [1, %d]", fn, P, LVC_PAIR_MAX);
+  // the shape, with the path left open (the pair limit decides it below); a run records, so save_every >= 1
+  p.base = lvc_plan(fn, 2 * P, nel, M, dims, path_req == LVC_RESIDENT ? LVC_AUTO : path_req, nsteps, save_every, true);
+  if (p.base.refused) return refuse("%s", p.base.msg);
+  if (!blocks) return refuse("%s: null blocks", fn);
+  if (!(nblk >= 1 && nblk <= 1 + M)) return refuse("%s: nblk=%d outside [1, %d]", fn, nblk, 1 + M);
+  for (int k = 0; k < nblk; ++k)
+    if (!(blocks[k] >= 0 && blocks[k] <= M)) return refuse("%s: blocks[%d]=%d outside [0, %d]", fn, k, blocks[k], M);
+  const long D = p.base.dev.D;
+  const long limit = lvc_pair_resident_limit(M);
+  const bool fits = D <= limit;
+  if (path_req == LVC_RESIDENT && !fits)
+    return refuse("%s: the pair resident path needs D <= %ld with %d modes (D = %ld)", fn, limit, M, D);
+  p.refused = 0;
+  p.base.path = path_req == LVC_AUTO ? (fits ? LVC_RESIDENT : LVC_STAGED) : path_req;
+  p.P = (int)P;
+  p.blocks.nblk = nblk;
+  for (int k = 0; k <= LVC_MAX_MODES; ++k) p.blocks.r[k] = k < nblk ? blocks[k] : 0;
+  p.rows = nel <= LVC_PAIR_REG_NEL ? nel : 1;
+  p.passes = nel / p.rows;
+  p.nv = 2 * nel * p.rows;
+  p.nrec = nblk * nel * nel;
+  p.part = LvcLaunch{(unsigned)p.base.G, (unsigned)(nblk * p.passes), (unsigned)P, LVC_TILE, 0};
+  p.fin = LvcLaunch{(unsigned)P, 1, 1, LVC_TILE, 0};
+  if (fits) {
+    const size_t vec = (size_t)D * 16;
+    p.lds_ket1 = vec;
+    p.lds_bra0 = 2 * vec;
+    p.lds_bra1 = 3 * vec;
+    p.lds_tab = 4 * vec;
+    p.lds_wave = p.lds_tab + (size_t)(1 + M) * nel * nel * 16;
+    p.lds_tile = p.lds_wave + lvc_align16((size_t)(LVC_RES_TPB / 64) * LVC_PAIR_NV_MAX * 8);
+    p.resident = LvcLaunch{(unsigned)P, 1, 1, LVC_RES_TPB,
+                           p.lds_tile + lvc_align16((size_t)lvc_ceil(LVC_PAIR_RESIDENT_MAX_D, LVC_TILE) *
+                                                    LVC_PAIR_NV_MAX * 8)};
+  }
+  p.ws_part = p.base.ws_part;
+  p.ws_part_bytes = lvc_align16((size_t)P * nblk * p.passes * p.base.G * p.nv * 8);
+  p.ws_total = p.ws_part + p.ws_part_bytes;
   return p;
 }
 

@@ -579,6 +579,56 @@ def lvc_observe(psi, nel, dims):
     return obs
 
 
+def _lvc_blocks(blocks):
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.intc).reshape(-1))
+    if b.size < 1:
+        raise ValueError("lvc: at least one block is needed")
+    return b
+
+
+def lvc_pair_observe(psi, nel, dims, blocks):
+    """The pair records rec [P, nblk, nel, nel] of the pairs psi [P, 2, D] (ket, bra) (qd_lvc_pair_observe): block r is
+    R_r[a, b] = sum_n L_r[a, n] conj(bra[b, n]) with L_0 = ket and L_{j+1} = x_j ket, so <bra| A (x) 1 |ket> = tr(A R_0)
+    and <bra| A (x) x_j |ket> = tr(A R_{j+1}).  blocks: host integers in [0, M]."""
+    import torch
+    from . import _lib
+    b = _lvc_blocks(blocks)
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d = np.ascontiguousarray(np.asarray(dims, dtype=np.intc).reshape(-1))
+    if psi.dim() != 3 or psi.shape[1] != 2:
+        raise ValueError(f"lvc_pair_observe: psi must be [P, 2, D], got {tuple(psi.shape)}")
+    rec = torch.empty((psi.shape[0], b.size, int(nel), int(nel)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_pair_observe(_lib.ptr(psi), psi.shape[0], int(nel), d.size, d.ctypes.data, b.size,
+                                             b.ctypes.data, _lib.ptr(rec), _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_pair_observe")
+    return rec
+
+
+def lvc_pair_rk4(psi, nel, dims, omega, Hel, W, dt, nsteps, save_every=1, blocks=(0,), path="auto", rec=None):
+    """lvc_rk4 of both states of the pairs psi [P, 2, D] in place with the pair record of lvc_pair_observe at t0 and
+    after every save_every steps (qd_lvc_pair_rk4).  Returns rec [P, nsteps // save_every + 1, nblk, nel, nel]; rec may
+    be passed in (a graph capture replays into the same buffer).  path: "auto", "staged" or "resident"."""
+    import torch
+    from . import _lib
+    dev = psi.device
+    _lib.ensure_device(dev)
+    d, w = _lvc_arrays(dims, omega)
+    b = _lvc_blocks(blocks)
+    if psi.dim() != 3 or psi.shape[1] != 2:
+        raise ValueError(f"lvc_pair_rk4: psi must be [P, 2, D], got {tuple(psi.shape)}")
+    nsave = nsteps // save_every if save_every > 0 else 0
+    if rec is None:
+        rec = torch.empty((psi.shape[0], nsave + 1, b.size, int(nel), int(nel)), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qd_lvc_pair_rk4(_lib.ptr(psi), psi.shape[0], int(nel), d.size, d.ctypes.data, w.ctypes.data,
+                                         _lib.ptr(Hel), _lib.ptr(W), float(dt), int(nsteps), int(save_every), b.size,
+                                         b.ctypes.data, _lib.ptr(rec), LVC_PATHS[path], _lib.stream_ptr(dev))
+    _lib.check(rc, "qd_lvc_pair_rk4")
+    return rec
+
+
 def _jump(f, i, dim, isherm=True):
     """phys.py:513-525 as a dense array: |f><i| (+ |i><f| when isherm), one diagonal entry for f == i."""
     A = np.zeros((dim, dim))
@@ -841,8 +891,9 @@ class LVC:
 
 class LVCSolver(SESolver):
     """What LVC.wavepacket_dynamics() returns: SESolver whose run() propagates matrix-free on the GPU (qd_lvc_rk4).
-    self.H is the model's sparse H, built on first access (the inherited correlation functions and pulsed runs use it,
-    at sizes the dense path can hold)."""
+    and whose correlation functions stay matrix-free where the operators are held as factors (qd_lvc_pair_rk4).
+    self.H is the model's sparse H, built on first access (correlation functions and pulsed runs with D x D operands
+    use it, at sizes the dense path can hold)."""
 
     def __init__(self, model):
         self.model = model
@@ -903,6 +954,168 @@ class LVCSolver(SESolver):
         if fac is None:
             return None
         return fac[0].reshape(1, m.nel, m.nel), [fac[1]], lambda t: [complex(pulse.efield(t))]
+
+    # ------------------------------------------------------------ correlation functions, matrix-free
+    def _corr_factors(self, name, oplist):
+        """[(A [nel, nel], block)] of the operands where every one is held as factors: an LVCOp of the model's space
+        (block 0 for A (x) 1, j + 1 for A (x) x_j) or an [nel, nel] array meaning A (x) 1.  None where any operand is a
+        D x D matrix, dense or sparse: the call then goes to SESolver's method on self.H."""
+        from ._util import issparse, to_numpy
+        m = self.model
+        fac, dense = [], False
+        for i, op in enumerate(oplist):
+            if isinstance(op, LVCOp):
+                if op.dims != tuple(m.fock_dims) or op.nel != m.nel:
+                    raise ValueError(f"{name}: operator {i} is an LVCOp of another space than the model's")
+                fac.append((op.A, 0 if op.mode is None else int(op.mode) + 1))
+                continue
+            shape = tuple(op.shape) if hasattr(op, "shape") else np.shape(op)
+            if not issparse(op) and shape == (m.nel, m.nel):
+                fac.append((to_numpy(op, np.complex128), 0))
+            else:
+                dense = True   # SESolver checks its shape
+        return None if dense else fac
+
+    @staticmethod
+    def _corr_host_ops(oplist):
+        return [op.tocsr() if isinstance(op, LVCOp) else op for op in oplist]
+
+    @staticmethod
+    def _corr_product(name, b, c):
+        """The factors of b c for b, c held as factors; two coordinate factors have no single-block form."""
+        if b[1] and c[1]:
+            raise NotImplementedError(f"{name}: the product of two coordinate factors (A (x) x_j)(B (x) x_k) is no "
+                                      "single block of the pair record; pass D x D operators for the dense path")
+        return b[0] @ c[0], b[1] or c[1]
+
+    def _corr_psi0(self, name, psi0):
+        from ._util import to_numpy
+        p0 = to_numpy(psi0, np.complex128).reshape(-1)
+        if p0.size != self.model.dim:
+            raise ValueError(f"{name}: psi0 has {p0.size} elements, expected {self.model.dim}")
+        return p0
+
+    def _factor_tables(self, fac, dev):
+        """(omega, Hel, W) with which lvc_apply applies the factor alone: Hel = A for A (x) 1, W[j] = A for A (x) x_j."""
+        import torch
+        m = self.model
+        A, blk = fac
+        Hel = np.zeros((m.nel, m.nel), dtype=complex)
+        W = np.zeros((m.nmodes, m.nel, m.nel), dtype=complex)
+        if blk == 0:
+            Hel[:] = A
+        else:
+            W[blk - 1] = A
+        return np.zeros(m.nmodes), torch.from_numpy(Hel).to(dev), torch.from_numpy(W).to(dev)
+
+    def _pair_bytes(self):
+        """Device bytes one pair takes in a pair run: the pair, its copy while it is assembled, the two stage vectors of
+        both states, and the partial rows of one block."""
+        m = self.model
+        tiles = -(-m.nvib // 256)
+        return 8 * 16 * m.dim + min(tiles, 1024) * 2 * m.nel * m.nel * 8
+
+    def _pair_corr(self, name, fac, psi_t, dt, ntau, path, chunk=None):
+        """corr [B, ntau] of the states psi_t [B, D] (device) for the factors [a, b, c]: ket = c psi and bra = a^+ psi by
+        lvc_apply, one lvc_pair_rk4 per chunk of pairs with the single block of b, the contraction on the host."""
+        import torch
+        m = self.model
+        dev = psi_t.device
+        B = psi_t.shape[0]
+        if chunk is None:
+            free = torch.cuda.mem_get_info(dev)[0]
+            per = self._pair_bytes()
+            chunk = min(B, 32767, (free // 4) // per)
+            if chunk < 1:
+                raise MemoryError(f"{name}: one pair of D = {m.dim} needs {per} bytes of states and scratch, a quarter "
+                                  f"of the free device memory is {free // 4} bytes")
+        chunk = max(1, min(int(chunk), 32767))
+        (a, a_blk), (b, b_blk), c = fac
+        t_ket = self._factor_tables(c, dev)
+        t_bra = self._factor_tables((a.conj().T, a_blk), dev)   # x_j is Hermitian
+        Hel = torch.from_numpy(np.ascontiguousarray(m.Hel())).to(dev)
+        W = torch.from_numpy(np.ascontiguousarray(m.Wmats())).to(dev)
+        corr = np.zeros((B, ntau), dtype=complex)
+        for i0 in range(0, B, chunk):
+            src = psi_t[i0:i0 + chunk].contiguous()
+            pairs = torch.empty((src.shape[0], 2, m.dim), dtype=torch.complex128, device=dev)
+            pairs[:, 0] = lvc_apply(src, m.nel, m.fock_dims, *t_ket)
+            pairs[:, 1] = lvc_apply(src, m.nel, m.fock_dims, *t_bra)
+            rec = lvc_pair_rk4(pairs, m.nel, m.fock_dims, m.omegas, Hel, W, dt, ntau - 1, save_every=1,
+                               blocks=(b_blk,), path=path)
+            corr[i0:i0 + chunk] = np.einsum("ab,...ba->...", b, rec[:, :, 0].cpu().numpy())
+            del pairs, rec
+        return corr
+
+    def correlation_3op_1t(self, psi0, oplist, dt, Nt, device=None, path="auto"):
+        """<A B(t) C> at t = 0 .. (Nt-1) dt (mol.py:1475-1501): complex ndarray (Nt,), corr[j] = <bra(j)| b |ket(j)>
+        with ket = c psi0 and bra = a^+ psi0 after j steps.  Where every operator is held as factors (an LVCOp of the
+        model's space, or an [nel, nel] array meaning A (x) 1) the call is matrix-free: c and a^+ by lvc_apply, one
+        lvc_pair_rk4 with the block of b.  Any D x D operand (dense or sparse) takes SESolver's method on self.H, an
+        LVCOp beside it converted with tocsr()."""
+        _check_corr_args("correlation_3op_1t", oplist, 3, Nt=Nt)
+        fac = self._corr_factors("correlation_3op_1t", oplist)
+        if fac is None:
+            return SESolver.correlation_3op_1t(self, psi0, self._corr_host_ops(oplist), dt, Nt)
+        return self._corr_1t("correlation_3op_1t", psi0, fac, dt, Nt, device, path)
+
+    def _corr_1t(self, name, psi0, fac, dt, Nt, device, path):
+        import torch
+        from ._util import default_device
+        if path not in LVC_PATHS:
+            raise ValueError(f"{name}: path={path!r}, expected 'auto', 'staged' or 'resident'")
+        p0 = self._corr_psi0(name, psi0)
+        dev = torch.device(device) if device is not None else default_device()
+        psi = torch.from_numpy(p0.reshape(1, -1).copy()).to(dev)
+        return self._pair_corr(name, fac, psi, dt, int(Nt), path)[0]
+
+    def correlation_3op_2t(self, psi0, oplist, dt, Nt, Ntau, device=None, path="auto", _chunk=None):
+        """<A(t) B(t+tau) C(t)> (mol.py:1503-1536): complex ndarray (Nt, Ntau).  With operators held as factors the
+        states psi(t_i) are the snapshots of one lvc_rk4 run and stay on the device; their Nt pairs go through the pair
+        run in chunks whose states and scratch stay under a quarter of the free device memory (MemoryError where one
+        pair does not fit).  D x D operands as in correlation_3op_1t."""
+        _check_corr_args("correlation_3op_2t", oplist, 3, Nt=Nt, Ntau=Ntau)
+        fac = self._corr_factors("correlation_3op_2t", oplist)
+        if fac is None:
+            return SESolver.correlation_3op_2t(self, psi0, self._corr_host_ops(oplist), dt, Nt, Ntau)
+        return self._corr_2t("correlation_3op_2t", psi0, fac, dt, Nt, Ntau, device, path, _chunk)
+
+    def _corr_2t(self, name, psi0, fac, dt, Nt, Ntau, device, path, chunk):
+        import torch
+        from ._util import default_device
+        if path not in LVC_PATHS:
+            raise ValueError(f"{name}: path={path!r}, expected 'auto', 'staged' or 'resident'")
+        m = self.model
+        p0 = self._corr_psi0(name, psi0)
+        dev = torch.device(device) if device is not None else default_device()
+        psi = torch.from_numpy(p0.reshape(1, -1).copy()).to(dev)
+        psi_t = psi.clone()
+        if Nt > 1:
+            Hel = torch.from_numpy(np.ascontiguousarray(m.Hel())).to(dev)
+            W = torch.from_numpy(np.ascontiguousarray(m.Wmats())).to(dev)
+            snap, _ = lvc_rk4(psi, m.nel, m.fock_dims, m.omegas, Hel, W, dt, int(Nt) - 1, save_every=1, observe=False)
+            psi_t = torch.cat([psi_t, snap[0]], dim=0)
+        return self._pair_corr(name, fac, psi_t, dt, int(Ntau), path, chunk)
+
+    def correlation_4op_1t(self, psi0, oplist, dt=0.005, Nt=1, device=None, path="auto"):
+        """<A B(t) C(t) D> (mol.py:1538-1554): the 3-operator form with [a, b c, d].  Matrix-free where all four are
+        held as factors and b c is one: the product of two coordinate factors raises NotImplementedError."""
+        _check_corr_args("correlation_4op_1t", oplist, 4, Nt=Nt)
+        fac = self._corr_factors("correlation_4op_1t", oplist)
+        if fac is None:
+            return SESolver.correlation_4op_1t(self, psi0, self._corr_host_ops(oplist), dt, Nt)
+        fac = [fac[0], self._corr_product("correlation_4op_1t", fac[1], fac[2]), fac[3]]
+        return self._corr_1t("correlation_4op_1t", psi0, fac, dt, Nt, device, path)
+
+    def correlation_4op_2t(self, psi0, oplist, dt=0.005, Nt=1, Ntau=1, device=None, path="auto", _chunk=None):
+        """<A(t) B(t+tau) C(t+tau) D(t)> (mol.py:1556-1566): the 3-operator form with [a, b c, d], as
+        correlation_4op_1t."""
+        _check_corr_args("correlation_4op_2t", oplist, 4, Nt=Nt, Ntau=Ntau)
+        fac = self._corr_factors("correlation_4op_2t", oplist)
+        if fac is None:
+            return SESolver.correlation_4op_2t(self, psi0, self._corr_host_ops(oplist), dt, Nt, Ntau)
+        fac = [fac[0], self._corr_product("correlation_4op_2t", fac[1], fac[2]), fac[3]]
+        return self._corr_2t("correlation_4op_2t", psi0, fac, dt, Nt, Ntau, device, path, _chunk)
 
     def run_batch(self, psi0s, dt=0.01, Nt=1, e_ops=None, nout=1, t0=0.0, store_states=True, device=None,
                   path="auto", edip=None, pulse=None, sample="hold"):

@@ -13,6 +13,12 @@ One JSON line per (shape, path): the median, minimum and maximum over --repeats 
 each admitted path) next to the undriven qd_lvc_rk4 on the same model and path, whose ratio is the line's
 `vs_undriven`; --scan replaces the shape list by the models between D = 960 and 2046 in one to six modes, for the
 driven resident / staged crossover.  Stage mode moves 16 state streams per step where the Horner step moves 12.
+
+--pair times qd_lvc_pair_rk4 (one pair, one block, a record after every step) on 16^3, 24^3 and 20^5 on each admitted
+path, next to two baselines on the same two states and path: qd_lvc_rk4 without observables (the propagation floor,
+`vs_floor`) and qd_lvc_rk4 with its full record every step (`vs_full_record`, the only in-run reduction there was).
+--pair --scan replaces the shapes by models between D = 480 and 1023 in one to six modes, for the pair resident /
+staged crossover (LVC_PAIR_RESIDENT_MAX_D).  Results of these go to profiles/lvc_pair/.
 """
 from __future__ import annotations
 
@@ -33,6 +39,11 @@ SHAPES = [(3, (16, 16)), (3, (24, 24, 24)), (3, (16, 16, 16, 16)), (3, (32, 32, 
 SCAN = [(3, (342,)), (3, (512,)), (3, (682,)), (3, (18, 19)), (3, (22, 23)), (3, (26, 26)), (3, (7, 7, 7)),
         (3, (8, 8, 8)), (3, (8, 9, 9)), (3, (4, 4, 4, 5)), (3, (5, 5, 5, 5)), (3, (3, 3, 3, 3, 3, 2)),
         (3, (3, 3, 3, 3, 4, 2))]
+PAIR_SHAPES = [(3, (16, 16, 16)), (3, (24, 24, 24)), (3, (20, 20, 20, 20, 20))]
+# pair resident against pair staged below the pair resident limit, one to six modes (--pair --scan)
+PAIR_SCAN = [(3, (170,)), (3, (256,)), (3, (341,)), (3, (13, 13)), (3, (16, 16)), (3, (18, 18)), (3, (6, 6, 6)),
+             (3, (7, 7, 6)), (3, (4, 4, 4, 4)), (3, (4, 4, 4, 5)), (3, (3, 3, 3, 3, 3)), (3, (2, 2, 2, 2, 2, 5)),
+             (3, (3, 3, 3, 3, 2, 2))]
 DENSE_MAX_D = 8192
 MAX_STEPS = 50000
 
@@ -82,6 +93,49 @@ def measure(torch, fn, window, repeats):
     return steps, float(np.median(ts)), float(min(ts)), float(max(ts))
 
 
+def pair_lines(torch, args, lines, nel, dims, D, omega, Hd, Wd, dt, psi0, lvc_rk4, lvc_pair_rk4):
+    """The --pair lines of one shape: per admitted path the pair run with one block and a record after every step, and
+    qd_lvc_rk4 of the same two states on that path without observables and with its full record every step."""
+    two = torch.cat([psi0, psi0.roll(1, 1)], dim=0)
+    for path in ("staged", "resident"):
+        pairs = two.clone().reshape(1, 2, D)
+        recs = {}
+
+        def pfn(steps, pairs=pairs, path=path, recs=recs):
+            if steps not in recs:           # the record buffer is no part of the timed call
+                recs[steps] = torch.empty((1, steps + 1, 1, nel, nel), dtype=torch.complex128, device=pairs.device)
+            lvc_pair_rk4(pairs, nel, dims, omega, Hd, Wd, dt, steps, save_every=1, blocks=(0,), path=path,
+                         rec=recs[steps])
+        try:
+            pfn(1)
+        except ValueError:                  # the pair plan does not admit the path at this D
+            continue
+        a, b = two.clone(), two.clone()
+        obs = {}
+
+        def floor(steps, a=a, path=path):
+            lvc_rk4(a, nel, dims, omega, Hd, Wd, dt, steps, observe=False, path=path)
+
+        def full(steps, b=b, path=path, obs=obs):
+            if steps not in obs:
+                obs[steps] = torch.empty((2, steps + 1, nel * nel * (1 + len(dims)) + len(dims)),
+                                         dtype=torch.complex128, device=b.device)
+            lvc_rk4(b, nel, dims, omega, Hd, Wd, dt, steps, save_every=1, store=False, path=path, obs=obs[steps])
+        res = {}
+        for name, fn in ((f"lvc_{path}_floor", floor), (f"lvc_{path}_full_record", full), (f"lvc_pair_{path}", pfn)):
+            steps, med, lo, hi = measure(torch, fn, args.window, args.repeats)
+            res[name] = med
+            rec = {"bench": "lvc_pair", "nel": nel, "dims": list(dims), "D": D, "path": name, "steps": steps,
+                   "repeats": args.repeats, "us_per_step": med * 1e6, "us_per_step_min": lo * 1e6,
+                   "us_per_step_max": hi * 1e6}
+            if name.startswith("lvc_pair_"):
+                rec["vs_floor"] = med / res[f"lvc_{path}_floor"]
+                rec["vs_full_record"] = med / res[f"lvc_{path}_full_record"]
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -90,14 +144,16 @@ def main():
     ap.add_argument("--shapes", default=None, help='e.g. "16,16;24,24,24" (nel = 3)')
     ap.add_argument("--driven", action="store_true", help="time qd_lvc_driven_rk4 against qd_lvc_rk4")
     ap.add_argument("--scan", action="store_true", help="the crossover scan's shapes instead of the default list")
+    ap.add_argument("--pair", action="store_true", help="time qd_lvc_pair_rk4 against qd_lvc_rk4 of the same states")
     args = ap.parse_args()
     import torch
     from pyqed_amd import _lib
-    from pyqed_amd.mol import lvc_driven_rk4, lvc_rk4, tdse_rk4
+    from pyqed_amd.mol import lvc_driven_rk4, lvc_pair_rk4, lvc_rk4, tdse_rk4
     if not torch.cuda.is_available():
         raise SystemExit("bench_lvc needs a GPU: no timing is taken on a CPU")
     dev = torch.device("cuda", 0)
-    shapes = (SCAN if args.scan else SHAPES) if args.shapes is None else [(3, tuple(int(v) for v in s.split(","))) for s in
+    default = (PAIR_SCAN if args.scan else PAIR_SHAPES) if args.pair else (SCAN if args.scan else SHAPES)
+    shapes = default if args.shapes is None else [(3, tuple(int(v) for v in s.split(","))) for s in
                                                  args.shapes.split(";")]
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
     lines = []
@@ -113,6 +169,9 @@ def main():
         psi0 = torch.zeros((1, D), dtype=torch.complex128, device=dev)
         psi0[0, (nel - 1) * (D // nel)] = 1.0
         runs = []
+        if args.pair:
+            pair_lines(torch, args, lines, nel, dims, D, omega, Hd, Wd, dt, psi0, lvc_rk4, lvc_pair_rk4)
+            continue
         for path in ("staged", "resident"):
             psi = psi0.clone()
 
